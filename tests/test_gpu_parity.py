@@ -384,7 +384,7 @@ def test_full_size_presets_match_the_oracle_on_a_sample(config):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--config", str(config), "--steps", "1", "--warmup", "0",
-           "--parity-only", "--cpu-sample", "200000"]
+           "--full", "--parity-only", "--cpu-sample", "200000"]
     p = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
@@ -405,13 +405,13 @@ def test_full_size_presets_match_the_oracle_on_a_sample(config):
 def test_every_read_of_the_headline_shard_matches_the_oracle():
     """The workload the bench line is quoted on, exhaustively: all 25 000 000 reads of the headline shard (BASELINE.json
     configs[2]: 150 bp pairs, k = 23) through the kernels the bench times, then the oracle -- all host cores, the same table --
-    on every one of them: return values, l / m / h and corrected bases (`bench.py --parity-only --parity-full`)."""
+    on every one of them: return values, l / m / h and corrected bases (`bench.py --full --parity-only --parity-full`)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--config", "2", "--steps", "1", "--warmup", "0",
-           "--parity-only", "--parity-full", "--cpu-sample", "200000"]
+           "--full", "--parity-only", "--parity-full", "--cpu-sample", "200000"]
     p = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     d = json.loads([ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")][0])

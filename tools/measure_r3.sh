@@ -62,6 +62,6 @@ cp $OUT/r3_traffic.json profiles/r3_traffic.json   # (on the box: so that the be
 { echo "# $(nproc) cores, $(grep MemTotal /proc/meminfo), /tmp on: $(df -T /tmp | tail -1)"; echo "## tools/mb/iob /tmp 4"; timeout 600 tools/mb/iob /tmp 4; echo "## tools/mb/iob /dev/shm 4"; timeout 600 tools/mb/iob /dev/shm 4; echo "## tools/mb/iob2 /tmp 4"; timeout 600 tools/mb/iob2 /tmp 4; } > $OUT/r3_host_io_microbench.txt 2>&1
 rm -f /tmp/iob.dat /dev/shm/iob.dat
 for c in $CONFIGS; do
-  timeout 1800 python bench.py --config $c > $OUT/r3_bench_config$c.json 2> $OUT/r3_bench_config$c.err
+  timeout 1800 python bench.py --config $c --full > $OUT/r3_bench_config$c.json 2> $OUT/r3_bench_config$c.err
   python tools/fmt_bench.py $OUT/r3_bench_config$c.json
 done

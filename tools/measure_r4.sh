@@ -14,6 +14,6 @@ for c in $CONFIGS; do
   (cd /tmp && timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python $REPO/bench.py --config $c --no-extras --steps 3 --warmup 1 > $REPO/$OUT/r4_config${c}_bench_under_rocprof.json 2> /tmp/prof_stats.err)
   python tools/prof_summary.py stats /tmp/prof_stats > $OUT/r4_config${c}_bench_kernel_stats.txt
   python tools/step_timeline.py /tmp/prof_stats > $OUT/r4_config${c}_step_timeline.txt
-  RC_BENCH_WRITE_TRAFFIC=$REPO/$OUT/r4_traffic.json RC_BENCH_PMC_TIMEOUT=1500 timeout 3000 python bench.py --config $c > $OUT/r4_bench_config$c.json 2> $OUT/r4_bench_config$c.err
+  RC_BENCH_WRITE_TRAFFIC=$REPO/$OUT/r4_traffic.json RC_BENCH_PMC_TIMEOUT=1500 timeout 3000 python bench.py --config $c --full > $OUT/r4_bench_config$c.json 2> $OUT/r4_bench_config$c.err
   python tools/fmt_bench.py $OUT/r4_bench_config$c.json
 done
