@@ -140,6 +140,25 @@ int rc_table_layout(const rc_ctx *ctx);
 /* bytes of HBM held by the table, number of buckets, number of stored entries */
 int rc_table_stats(const rc_ctx *ctx, uint64_t *bytes, uint64_t *buckets, uint64_t *entries);
 
+/* ---- k-mer count spectrum (what `jellyfish histo` prints of a Jellyfish database) ---------------------------------------------
+ * A spectrum with bound max_bin >= 1 is uint64_t freq[max_bin + 1]: freq[0] = 0; freq[c], 1 <= c < max_bin, the number of
+ * distinct canonical k-mers whose count is exactly c; freq[max_bin] the number whose count is >= max_bin.  The statistics
+ * are exact whatever max_bin is (total = the sum of the counts).  No reference counterpart: the reference reads a
+ * Jellyfish database, which `jellyfish histo` summarises; this library counts without one. */
+typedef struct {
+    uint64_t distinct, total, unique, max_count;
+} rc_spectrum_stats;
+/* arms the counted spectrum with bound max_bin (0 = off, the default; at most 2^28): the next rc_table_count_finish /
+ * rc_table_count_finish_sharded (ctxs[0]'s setting, result on ctxs[0]) bins every canonical k-mer it sees -- those below
+ * min_count included, with its full 32-bit count; k-mers holding a letter outside ACGT are left out, as by the counter.  The
+ * setting stays until changed; the result stays in host memory until the next rc_table_count_begin. */
+int rc_table_count_spectrum(rc_ctx *ctx, uint32_t max_bin);
+/* source 0: the live entries of the current table (the counts rc_table_lookup returns; any table: counted, loaded, built,
+ * shared or replicated) -- RC_STATUS_STATE without a table.  source 1: the counted spectrum of the last finish, folded
+ * into max_bin if that is below its bound -- RC_STATUS_STATE if none was armed, RC_STATUS_ARG above the armed bound.
+ * stats may be NULL. */
+int rc_table_spectrum(rc_ctx *ctx, int source, uint64_t *freq, uint32_t max_bin, rc_spectrum_stats *stats);
+
 /* ---- run parameters (globals of main.cpp:17-30) ----------------------------------------------- */
 /* replaces main.cpp:310-358 (ERROR_RATE estimation).  Uses the entries parsed by the last
  * rc_table_load_jfdump() in file order -- or, for a table that was counted here or built from

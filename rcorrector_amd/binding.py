@@ -15,6 +15,7 @@ ABI_SYMBOLS = [
     "rc_table_count_begin", "rc_table_count_add", "rc_table_count_add_device", "rc_table_count_finish",
     "rc_table_count_keep", "rc_table_count_arenas", "rc_table_count_release", "rc_table_count_park", "rc_table_count_finish_sharded", "rc_submit_resident", "rc_wait_resident",
     "rc_table_count_reads_device", "rc_table_write_jfdump", "rc_table_share", "rc_table_replicate", "rc_table_replicate_async", "rc_table_lookup", "rc_table_export", "rc_table_digest", "rc_table_layout", "rc_table_stats",
+    "rc_table_count_spectrum", "rc_table_spectrum",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
@@ -64,6 +65,10 @@ class _ResidentBatch(C.Structure):
                 ("off", C.c_void_p), ("qual_bits", C.c_void_p),
                 ("ret", C.c_void_p), ("l", C.c_void_p), ("m", C.c_void_p), ("h", C.c_void_p),
                 ("fix_pos", C.c_void_p), ("fix_chr", C.c_void_p), ("fix_cap", C.c_size_t), ("n_fix", C.c_size_t)]
+
+
+class _SpectrumStats(C.Structure):
+    _fields_ = [("distinct", C.c_uint64), ("total", C.c_uint64), ("unique", C.c_uint64), ("max_count", C.c_uint64)]
 
 
 class _DeviceBatch(C.Structure):
@@ -131,6 +136,8 @@ def load_library():
     L.rc_table_digest.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.rc_table_layout.argtypes = [vp]
     L.rc_table_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.rc_table_count_spectrum.argtypes = [vp, C.c_uint32]
+    L.rc_table_spectrum.argtypes = [vp, C.c_int, vp, C.c_uint32, C.POINTER(_SpectrumStats)]
     L.rc_estimate_error_rate.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.rc_bad_quality_from_hist.restype = C.c_char
     L.rc_bad_quality_from_hist.argtypes = [vp, vp, C.c_int32]
@@ -329,6 +336,23 @@ class Context:
         b, n, e = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
         self._ck(self._L.rc_table_stats(self._h, C.byref(b), C.byref(n), C.byref(e)))
         return {"bytes": b.value, "buckets": n.value, "entries": e.value}
+
+    # ---- k-mer count spectrum ----
+    def count_spectrum(self, max_bin=10000):
+        """Arms the counted spectrum (rc_table_count_spectrum): the next count_finish / count_finish_sharded bins every
+        k-mer it sees, those below min_count included, into max_bin + 1 bins (the last one: counts >= max_bin).  0: off."""
+        self._ck(self._L.rc_table_count_spectrum(self._h, int(max_bin)))
+
+    def kmer_spectrum(self, source="table", max_bin=10000):
+        """rc_table_spectrum: (uint64 array freq[max_bin + 1], {"distinct", "total", "unique", "max_count"}) of the current
+        table's live entries (source="table") or of what the last armed count saw (source="counted")."""
+        src = {"table": 0, "counted": 1}.get(source)
+        if src is None:
+            raise ValueError("source must be 'table' or 'counted'")
+        freq = np.zeros(int(max_bin) + 1, dtype=np.uint64)
+        st = _SpectrumStats()
+        self._ck(self._L.rc_table_spectrum(self._h, src, freq.ctypes.data, int(max_bin), C.byref(st)))
+        return freq, {"distinct": st.distinct, "total": st.total, "unique": st.unique, "max_count": st.max_count}
 
     # ---- run parameters ----
     def estimate_error_rate(self, wk=0.95):

@@ -629,6 +629,62 @@ int rc_table_digest(rc_ctx *ctx, uint64_t *digest)
     return RC_OK;
 }
 
+#define RC_SPEC_MAX_BIN (1u << 28)
+
+int rc_table_count_spectrum(rc_ctx *ctx, uint32_t max_bin)
+{
+    if (!ctx) return RC_ERR_ARG;
+    if (max_bin > RC_SPEC_MAX_BIN) {
+        rc_set_error(ctx, "count_spectrum: max_bin %u is above %u", max_bin, RC_SPEC_MAX_BIN);
+        return RC_ERR_ARG;
+    }
+    ctx->spec_arm = max_bin;
+    return RC_OK;
+}
+
+int rc_table_spectrum(rc_ctx *ctx, int source, uint64_t *freq, uint32_t max_bin, rc_spectrum_stats *stats)
+{
+    if (!ctx) return RC_ERR_ARG;
+    if (!freq || max_bin < 1 || max_bin > RC_SPEC_MAX_BIN || (source != 0 && source != 1)) {
+        rc_set_error(ctx, "spectrum: source must be 0 (table) or 1 (counted), max_bin 1..%u, freq not NULL", RC_SPEC_MAX_BIN);
+        return RC_ERR_ARG;
+    }
+    uint64_t st[4] = {0, 0, 0, 0};
+    if (source == 1) {
+        const std::vector<uint64_t> &S = ctx->spec_counted;
+        if (S.empty()) {
+            rc_set_error(ctx, "spectrum: no counted spectrum (rc_table_count_spectrum before rc_table_count_finish)");
+            return RC_ERR_STATE;
+        }
+        const size_t bound = S.size() - 5;
+        if (max_bin > bound) {
+            rc_set_error(ctx, "spectrum: max_bin %u is above the bound the count was armed with (%zu)", max_bin, bound);
+            return RC_ERR_ARG;
+        }
+        std::copy(S.begin(), S.begin() + max_bin, freq);
+        uint64_t last = 0;  // (counts >= max_bin: the higher bins folded into the last one)
+        for (size_t c = max_bin; c <= bound; ++c) last += S[c];
+        freq[max_bin] = last;
+        std::copy(S.begin() + bound + 1, S.end(), st);
+    } else {
+        if (!ctx->d_buckets) {
+            rc_set_error(ctx, "spectrum: no k-mer table loaded");
+            return RC_ERR_STATE;
+        }
+        RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+        const int rc = rc_table_spectrum_scan(ctx, max_bin, freq, st);
+        if (rc) return rc;
+    }
+    freq[0] = 0;
+    if (stats) {
+        stats->distinct = st[0];
+        stats->total = st[1];
+        stats->unique = st[2];
+        stats->max_count = st[3];
+    }
+    return RC_OK;
+}
+
 int rc_table_layout(const rc_ctx *ctx)
 {
     if (!ctx) return RC_ERR_ARG;

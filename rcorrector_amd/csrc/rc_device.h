@@ -323,3 +323,115 @@ __device__ __forceinline__ bool rc_table_slot_entry(const rc_table_view &T, size
         if (bb > b) return false;  // (not reached: the slot itself matches at the latest)
     }
 }
+
+// ---- k-mer count spectrum (rc_table_spectrum, rc_table_count_spectrum) ------------------------------------------------------
+// One accumulate routine for both sources (the live entries of a table, the run-length counts of the counter's key slices).
+// freq[min(count, max_bin)] += 1 per entry, with three homes for a bin:
+//   bins 1 and 2 (the peak of a counted / a stored spectrum): a ballot per call, summed in wave-uniform registers -- half to
+//     three quarters of all lanes carry one of them, and as LDS atomics they would serialise on a single word;
+//   bins 3 .. RC_SPEC_SMALL - 1 (the bulk of the rest): one sub-histogram per wave in LDS, so waves do not meet on a word;
+//   bins RC_SPEC_SMALL .. lds_bins - 1: the workgroup's histogram in LDS;
+//   bins >= lds_bins (max_bin beyond what LDS holds, only where counts are that large): straight to the device array, one
+//     atomic per distinct bin and wave (the lanes with the same bin are counted by a ballot).
+// The four statistics go through the same call: distinct, unique and the two peak bins by ballots, total and max per lane.
+#define RC_SPEC_SMALL 64
+#define RC_SPEC_LDS_BINS 16384  // bins a workgroup holds in LDS (64 KB); above max_bin + 1 = this, the global path takes over
+#define RC_SPEC_THREADS 256
+#define RC_SPEC_WAVES (RC_SPEC_THREADS / 64)
+
+struct rc_spec_acc {
+    uint64_t distinct = 0, unique = 0, n1 = 0, n2 = 0;  // wave-uniform (ballot counts)
+    uint64_t total = 0;                                 // per lane
+    uint32_t max_count = 0;                             // per lane
+};
+
+// MUST be called by every lane of the wavefront (ballots); `valid` = this lane has an entry with count c >= 1
+__device__ __forceinline__ void rc_spec_add(rc_spec_acc &A, bool valid, uint32_t c, uint32_t max_bin, uint32_t lds_bins, uint32_t *s_wave,
+                                            uint32_t *s_big, unsigned long long *__restrict__ g_freq)
+{
+    const uint32_t bin = c < max_bin ? c : max_bin;
+    A.distinct += (uint64_t)__popcll(__ballot(valid));
+    A.unique += (uint64_t)__popcll(__ballot(valid && c == 1));
+    A.n1 += (uint64_t)__popcll(__ballot(valid && bin == 1));
+    A.n2 += (uint64_t)__popcll(__ballot(valid && bin == 2));
+    if (valid) {
+        A.total += c;
+        A.max_count = c > A.max_count ? c : A.max_count;
+        if (bin >= 3 && bin < lds_bins) {
+            if (bin < RC_SPEC_SMALL)
+                atomicAdd(&s_wave[bin], 1u);
+            else
+                atomicAdd(&s_big[bin - RC_SPEC_SMALL], 1u);
+        }
+    }
+    const bool glob = valid && bin >= 3 && bin >= lds_bins;
+    unsigned long long pend = __ballot(glob);
+    while (pend) {  // (wave-uniform loop over the distinct large bins of the wavefront)
+        const int leader = __ffsll(pend) - 1;
+        const uint32_t vb = (uint32_t)__shfl((int)bin, leader);
+        const unsigned long long m = __ballot(glob && bin == vb);
+        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&g_freq[vb], (unsigned long long)__popcll(m));
+        pend &= ~m;
+    }
+}
+
+// the workgroup's LDS: RC_SPEC_WAVES sub-histograms of RC_SPEC_SMALL bins, then (dynamic) lds_bins - RC_SPEC_SMALL words
+__device__ __forceinline__ void rc_spec_zero(uint32_t *s_small, uint32_t *s_big, uint32_t lds_bins)
+{
+    for (uint32_t i = threadIdx.x; i < RC_SPEC_WAVES * RC_SPEC_SMALL; i += blockDim.x) s_small[i] = 0;
+    for (uint32_t i = threadIdx.x; i + RC_SPEC_SMALL < lds_bins; i += blockDim.x) s_big[i] = 0;
+    __syncthreads();
+}
+
+// end of a workgroup: its statistics (one set of atomics per workgroup) and its non-zero bins into the device array
+// out = freq[max_bin + 1], then {distinct, total, unique, max_count}
+__device__ __forceinline__ void rc_spec_flush(rc_spec_acc &A, uint32_t max_bin, uint32_t lds_bins, uint32_t *s_small, uint32_t *s_big,
+                                              unsigned long long *__restrict__ out)
+{
+    __shared__ unsigned long long s_st[RC_SPEC_WAVES][4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned long long tot = A.total;
+    uint32_t mx = A.max_count;
+    for (int o = 32; o > 0; o >>= 1) {
+        tot += __shfl_xor(tot, o, 64);
+        const uint32_t y = (uint32_t)__shfl_xor((int)mx, o, 64);
+        mx = y > mx ? y : mx;
+    }
+    if (lane == 0) {
+        s_st[w][0] = A.distinct;
+        s_st[w][1] = tot;
+        s_st[w][2] = A.unique;
+        s_st[w][3] = mx;
+        s_small[w * RC_SPEC_SMALL + 1] += (uint32_t)A.n1;  // (the wave's own sub-histogram: no other wave writes it)
+        s_small[w * RC_SPEC_SMALL + 2] += (uint32_t)A.n2;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long d = 0, t = 0, u = 0, m = 0;
+        for (int i = 0; i < RC_SPEC_WAVES; ++i) {
+            d += s_st[i][0];
+            t += s_st[i][1];
+            u += s_st[i][2];
+            m = s_st[i][3] > m ? s_st[i][3] : m;
+        }
+        unsigned long long *st = out + (size_t)max_bin + 1;
+        if (d) {
+            atomicAdd(&st[0], d);
+            atomicAdd(&st[1], t);
+            if (u) atomicAdd(&st[2], u);
+            atomicMax(&st[3], m);
+        }
+    }
+    const uint32_t nsmall = lds_bins < RC_SPEC_SMALL ? lds_bins : RC_SPEC_SMALL;
+    for (uint32_t b = threadIdx.x; b < lds_bins; b += blockDim.x) {
+        uint32_t v;
+        if (b < nsmall) {
+            v = 0;
+#pragma unroll
+            for (int i = 0; i < RC_SPEC_WAVES; ++i) v += s_small[i * RC_SPEC_SMALL + b];
+        } else {
+            v = s_big[b - RC_SPEC_SMALL];
+        }
+        if (v) atomicAdd(&out[b], (unsigned long long)v);
+    }
+}

@@ -145,6 +145,16 @@ void apply_fixes_to_text(Arena &A1, Arena *A2, size_t bytes1, const uint32_t *fi
     }
 }
 
+bool write_histo(const char *path, const std::vector<uint64_t> &freq)
+{
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return false;
+    bool ok = true;
+    for (size_t c = 1; c < freq.size() && ok; ++c)
+        if (freq[c]) ok = fprintf(fp, "%zu %llu\n", c, (unsigned long long)freq[c]) > 0;
+    return fclose(fp) == 0 && ok;
+}
+
 void quality_histograms(const Block &b, int lpr, size_t room, std::vector<int32_t> &fh, std::vector<int32_t> &lh, int *total)
 {
     static char qbuf[MAX_READ_LENGTH];  // Reads::qual, reused from record to record

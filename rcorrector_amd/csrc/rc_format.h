@@ -152,6 +152,8 @@ static inline void put_record(B &out, const Arena &A, size_t r, bool fastq, int 
 // arena in the batch's device arena (0, or the size of arena 1 for second mates)
 void put_transcript(std::vector<char> &out, const Job &J, const Arena &A, size_t r, size_t gi, size_t ab, int k);
 
+// a k-mer count spectrum as `jellyfish histo` prints it: "<count> <frequency>\n" per non-zero bin, ascending; false: not written
+bool write_histo(const char *path, const std::vector<uint64_t> &freq);
 // GetBadQuality's two histograms over the records of one block (main.cpp:88-128), at most `room` of them
 void quality_histograms(const Block &b, int lpr, size_t room, std::vector<int32_t> &fh, std::vector<int32_t> &lh, int *total);
 

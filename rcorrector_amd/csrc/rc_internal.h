@@ -119,6 +119,11 @@ struct rc_ctx {
     // that was counted on this GPU are corrected where they lie (rc_submit_resident)
     bool cnt_keep = false;
     std::vector<rc_dbuf> kept_arenas, kept_chunks;
+    // k-mer count spectrum of the counter (rc_table_count_spectrum): the bound finish() bins to (0 = off), and what the last
+    // finish (on ctxs[0] of a sharded one) saw -- freq[bound + 1], then distinct, total, unique, max_count; empty: none
+    // since the last count_begin
+    uint32_t spec_arm = 0;
+    std::vector<uint64_t> spec_counted;
 
     // batch scratch
     rc_dbuf counts;   // int32 per arena byte
@@ -187,6 +192,10 @@ int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers)
 int rc_count_reads(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int min_count, int64_t *n_kmers);
 int rc_launch_selftest_bound(rc_ctx *ctx, const int32_t *d_c, size_t n, double e, int32_t *d_oi, double *d_od);
 int rc_launch_export(rc_ctx *ctx, uint64_t *d_codes, int32_t *d_counts, unsigned long long *d_n, size_t cap);
+// k-mer count spectrum (rc_device.h: rc_spec_add): the table's into host arrays freq[max_bin + 1], st[4]; one slice's run-length
+// counts added to d_out (freq[max_bin + 1], then the four statistics; zeroed by the caller) on stream st
+int rc_table_spectrum_scan(rc_ctx *ctx, uint32_t max_bin, uint64_t *freq, uint64_t *st);
+int rc_launch_spectrum_counts(rc_ctx *ctx, hipStream_t st, const uint32_t *d_cnt, size_t n, uint32_t max_bin, unsigned long long *d_out);
 int rc_table_entries_in_dump_order(rc_ctx *ctx, std::vector<uint64_t> *codes, std::vector<int32_t> *counts);
 int rc_error_rate_candidates(rc_ctx *ctx, const uint64_t *d_codes, size_t n, bool by_hash, size_t want, std::vector<uint64_t> *vals);
 int rc_table_codes_device(rc_ctx *ctx, uint64_t **d_codes, size_t *n);

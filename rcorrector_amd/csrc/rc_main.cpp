@@ -19,6 +19,8 @@
 // for packing / formatting.
 // -verbose prints the reference's per-read transcript (the -t 1 order) from rc_correct_batch_traced;
 // -write-dump FILE keeps the k-mer table as jellyfish-dump text; without -c the k-mers are counted here.
+// -histo FILE writes the k-mer count spectrum as `jellyfish histo` prints it (-histo-max: its last bin): without -c the
+// spectrum of every k-mer counted, singletons included; with -c that of the dump's entries.
 #include <fcntl.h>
 #include <malloc.h>
 #include <sys/stat.h>
@@ -53,6 +55,9 @@ static void print_help()
             "\t-batch INT: reads per GPU batch (default: 1048576)\n"
             "\t-inflight INT: batches in flight per GPU, 1-4 (default: 2, raised to 4 while the writer waits for the GPU)\n"
             "\t-write-dump STRING: also write the k-mer table as a jellyfish-dump text file\n"
+            "\t-histo STRING: also write the k-mer count spectrum (\"<count> <frequency>\" lines, as jellyfish histo prints them):\n"
+            "\t\twithout -c of every k-mer counted, count 1 included; with -c of the dump's k-mers\n"
+            "\t-histo-max INT: the spectrum's last bin, which holds the k-mers counted at least that often (default: 10000)\n"
             "\t-verbose-iter INT: threshold iterations recorded per read for -verbose (default: 64)\n");
 }
 
@@ -65,7 +70,8 @@ int main(int argc, char **argv)
     std::vector<ReadFile> &files = run.files, &mates = run.mates;
     int max_fix_per_k = 4, i;
     double wk = 0.95;
-    const char *dump = nullptr, *write_dump = nullptr;
+    const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr;
+    long histo_max = 10000;
     std::string od = "./";
     bool verbose = false;
     int t_flag = 0;
@@ -114,6 +120,10 @@ int main(int argc, char **argv)
         }
         else if (!strcmp("-write-dump", argv[i]))
             write_dump = argv[++i];
+        else if (!strcmp("-histo", argv[i]))
+            histo = argv[++i];
+        else if (!strcmp("-histo-max", argv[i]))
+            histo_max = atol(argv[++i]);
         else if (!strcmp("-packed", argv[i]))
             g_packed = true;
         else if (!strcmp("-h", argv[i])) {
@@ -129,6 +139,7 @@ int main(int argc, char **argv)
     // -verbose carries RC_TRACE_ITER_WORDS x trace-iter words per read through host and device
     // (9 KB per read at the default 64 iterations): small batches, or a real data set needs tens of GB
     if (verbose && batch_reads > (1u << 16)) batch_reads = 1u << 16;
+    if (histo && (histo_max < 1 || histo_max > (1l << 28))) die("rcorrector: -histo-max must be 1..%ld\n", 1l << 28);
     if (gpus < 1) gpus = 1;
     if (inflight < 1) inflight = 1;
     if (inflight > 8) inflight = 8;
@@ -337,6 +348,8 @@ int main(int argc, char **argv)
     if (!ahead) head = head_stats(run);
     std::thread warm([&]() { warm_buffers(run, head); });
     int64_t stored = 0;
+    // -histo without -c: the counter bins every k-mer it sees (on the first GPU's context, which holds a sharded count's result)
+    if (histo && !dump && rc_table_count_spectrum(ctx[0], (uint32_t)histo_max)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
     if (dump) {  // main.cpp:294-308: ONE Store, loaded once
         if (rc_table_load_jfdump(ctx[0], dump, &stored)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
     } else {
@@ -367,6 +380,11 @@ int main(int argc, char **argv)
         }
     }
     if (write_dump && rc_table_write_jfdump(ctx[0], write_dump, nullptr)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+    if (histo) {
+        std::vector<uint64_t> freq((size_t)histo_max + 1);
+        if (rc_table_spectrum(ctx[0], dump ? 0 : 1, freq.data(), (uint32_t)histo_max, nullptr)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+        if (!write_histo(histo, freq)) die("rcorrector: could not write %s\n", histo);
+    }
     fprintf(stderr, "Stored %d kmers\n", (int)stored);
     double rate = 0.01;
     if (rc_estimate_error_rate(ctx[0], wk, &rate)) die("rcorrector: %s\n", rc_last_error(ctx[0]));

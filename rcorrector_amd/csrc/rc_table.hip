@@ -530,6 +530,186 @@ int rc_launch_export(rc_ctx *ctx, uint64_t *d_codes, int32_t *d_counts, unsigned
     return RC_OK;
 }
 
+// ---- k-mer count spectrum (include/rcorrector_amd.h: rc_table_spectrum; accumulate routine in rc_device.h) --------------------
+static uint32_t rc_spec_lds_bins(uint32_t max_bin) { return max_bin < RC_SPEC_LDS_BINS ? max_bin + 1 : RC_SPEC_LDS_BINS; }
+static size_t rc_spec_lds_bytes(uint32_t lds_bins) { return lds_bins > RC_SPEC_SMALL ? (size_t)(lds_bins - RC_SPEC_SMALL) * 4 : 0; }
+#define RC_SPEC_UNROLL 4       // buckets per lane in flight (two 16-byte loads each)
+#define RC_SPEC_MAX_BLOCKS 2048
+
+// a PACKED entry stored `disp` buckets behind its home: live iff no slot of the buckets from its home on holds the same key
+// (same remainder bits, the displacement of that bucket) -- the first-match rule of rc_table_slot_entry, read from the
+// buckets in front of this one (this one's earlier slots were looked at in registers)
+__device__ __noinline__ bool rc_spec_packed_first(const rc_table_view &T, size_t b, uint32_t lo, uint32_t hi, uint32_t cmask, uint32_t mhi)
+{
+    const uint32_t d = (hi >> 27) & 15u;
+    const uint32_t key_hi = hi & mhi & ~(15u << 27);
+    for (uint32_t j = d; j >= 1; --j) {
+        const uint32_t *q = T.buckets + (b - j) * RC_BUCKET_DWORDS;
+        const uint32_t want = key_hi | ((d - j) << 27);
+        for (int i = 0; i < RC_PACKED_SLOTS; ++i)
+            if ((q[2 * i + 1] & cmask) != 0 && q[2 * i] == lo && (q[2 * i + 1] & mhi) == want) return false;
+    }
+    return true;
+}
+
+// table source: grid-stride over the buckets, each lane RC_SPEC_UNROLL whole buckets a step (a wavefront's load instruction
+// covers 64 consecutive buckets, 2 KB), the slots decoded in registers; the live rule is rc_table_slot_entry's
+__global__ __launch_bounds__(RC_SPEC_THREADS) void k_spectrum_table(rc_table_view T, uint32_t max_bin, uint32_t lds_bins,
+                                                                     unsigned long long *__restrict__ out)
+{
+    __shared__ uint32_t s_small[RC_SPEC_WAVES * RC_SPEC_SMALL];
+    extern __shared__ uint32_t s_big[];
+    rc_spec_zero(s_small, s_big, lds_bins);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t *s_wave = s_small + w * RC_SPEC_SMALL;
+    rc_spec_acc A;
+    const size_t nb = T.nbuckets_alloc, per_wave = 64 * RC_SPEC_UNROLL;
+    const size_t stride = (size_t)gridDim.x * RC_SPEC_WAVES * per_wave;
+    const uint32_t cmask = RC_PACKED_COUNT_MASK >> T.ext;
+    const uint32_t mhi = 0x7FFFFFFFu & ~cmask;  // remainder bits above the count, displacement
+    for (size_t base = ((size_t)blockIdx.x * RC_SPEC_WAVES + w) * per_wave; base < nb; base += stride) {
+        uint4 v[RC_SPEC_UNROLL][2];
+#pragma unroll
+        for (int u = 0; u < RC_SPEC_UNROLL; ++u) {
+            const size_t b = base + (size_t)u * 64 + lane;
+            v[u][0] = v[u][1] = make_uint4(0, 0, 0, 0);  // (beyond the table: no count in any slot of either layout)
+            if (b < nb) {
+                const uint4 *p = reinterpret_cast<const uint4 *>(T.buckets + b * RC_BUCKET_DWORDS);
+                v[u][0] = p[0];
+                v[u][1] = p[1];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RC_SPEC_UNROLL; ++u) {
+            const size_t b = base + (size_t)u * 64 + lane;
+            const uint32_t d[8] = {v[u][0].x, v[u][0].y, v[u][0].z, v[u][0].w, v[u][1].x, v[u][1].y, v[u][1].z, v[u][1].w};
+#ifdef RC_EXP_SPEC_LOAD_ONLY  // dev (WRONG spectrum): the bucket reads alone -- what the access pattern costs (tools/spectrum_time.py)
+            A.total += d[0] ^ d[1] ^ d[2] ^ d[3] ^ d[4] ^ d[5] ^ d[6] ^ d[7];
+            continue;
+#endif
+            if (T.layout) {
+#pragma unroll
+                for (int s = 0; s < RC_PACKED_SLOTS; ++s) {
+                    const uint32_t lo = d[2 * s], hi = d[2 * s + 1];
+                    uint32_t c = hi & cmask;
+                    bool live = c != 0;
+#pragma unroll
+                    for (int i = 0; i < s; ++i)
+                        if ((d[2 * i + 1] & cmask) != 0 && d[2 * i] == lo && ((d[2 * i + 1] ^ hi) & mhi) == 0) live = false;
+#ifndef RC_EXP_SPEC_NO_WALK  // dev (WRONG for tables with duplicate keys): without the walk over the buckets in front
+                    if (live && ((hi >> 27) & 15u)) live = rc_spec_packed_first(T, b, lo, hi, cmask, mhi);
+#endif
+                    if (live && c == cmask) {  // (rare) the full count lives in the table's prefix
+                        const uint32_t disp = (hi >> 27) & 15u;
+                        const uint64_t kk = rc_packed_key((uint32_t)(b - disp), lo, (hi & RC_PACKED_COUNT_MASK) >> (27 - T.ext), T.ext, T.k, T.nb_home);
+                        c = (uint32_t)rc_packed_overflow_count(T, kk);
+                    }
+                    rc_spec_add(A, live, c, max_bin, lds_bins, s_wave, s_big, out);
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < RC_WIDE_SLOTS; ++s) {
+                    const uint32_t c = d[3 * s + 2];
+                    bool live = c != 0;
+                    if (live) {
+                        const uint64_t kk = ((uint64_t)d[3 * s + 1] << 32) | d[3 * s];
+                        if (rc_home(kk, T.nb_home) == b) {  // the walk starts here: an earlier slot of this bucket with the same key wins
+#pragma unroll
+                            for (int i = 0; i < s; ++i)
+                                if (d[3 * i + 2] != 0 && d[3 * i] == d[3 * s] && d[3 * i + 1] == d[3 * s + 1]) live = false;
+                        } else {  // (displaced: the walk from the key's home, in memory)
+                            uint64_t key;
+                            int32_t cc;
+                            live = rc_table_slot_entry(T, b, s, &key, &cc);
+                        }
+                    }
+                    rc_spec_add(A, live, c, max_bin, lds_bins, s_wave, s_big, out);
+                }
+            }
+        }
+    }
+    rc_spec_flush(A, max_bin, lds_bins, s_small, s_big, out);
+}
+
+// counted source: the run-length counts of one key slice (what k_flag_keep filters), four per lane and step
+__global__ __launch_bounds__(RC_SPEC_THREADS) void k_spectrum_counts(const uint32_t *__restrict__ cnt, size_t n, uint32_t max_bin, uint32_t lds_bins,
+                                                                      unsigned long long *__restrict__ out)
+{
+    __shared__ uint32_t s_small[RC_SPEC_WAVES * RC_SPEC_SMALL];
+    extern __shared__ uint32_t s_big[];
+    rc_spec_zero(s_small, s_big, lds_bins);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t *s_wave = s_small + w * RC_SPEC_SMALL;
+    rc_spec_acc A;
+    const size_t nq = (n + 3) / 4, stride = (size_t)gridDim.x * RC_SPEC_WAVES * 64;
+    for (size_t base = ((size_t)blockIdx.x * RC_SPEC_WAVES + w) * 64; base < nq; base += stride) {
+        const size_t q = base + lane;
+        uint32_t c[4] = {0, 0, 0, 0};
+        if (q * 4 + 4 <= n) {
+            const uint4 x = reinterpret_cast<const uint4 *>(cnt)[q];
+            c[0] = x.x;
+            c[1] = x.y;
+            c[2] = x.z;
+            c[3] = x.w;
+        } else {
+            for (int j = 0; j < 4; ++j)
+                if (q * 4 + j < n) c[j] = cnt[q * 4 + j];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) rc_spec_add(A, c[j] != 0, c[j], max_bin, lds_bins, s_wave, s_big, out);
+    }
+    rc_spec_flush(A, max_bin, lds_bins, s_small, s_big, out);
+}
+
+static hipError_t rc_spec_allow_lds(const void *fn, size_t bytes)
+{
+    const size_t total = bytes + RC_SPEC_WAVES * RC_SPEC_SMALL * 4 + RC_SPEC_WAVES * 4 * 8;
+    if (total <= 65536) return hipSuccess;
+    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+// d_out: max_bin + 1 + 4 uint64, zeroed by the caller before the first launch; adds one slice's counts (stream st)
+int rc_launch_spectrum_counts(rc_ctx *ctx, hipStream_t st, const uint32_t *d_cnt, size_t n, uint32_t max_bin, unsigned long long *d_out)
+{
+    if (n == 0) return RC_OK;
+    if (reinterpret_cast<uintptr_t>(d_cnt) & 15u) {
+        rc_set_error(ctx, "spectrum: run-length counts not 16-byte aligned");
+        return RC_ERR_ARG;
+    }
+    const uint32_t lds = rc_spec_lds_bins(max_bin);
+    const size_t bytes = rc_spec_lds_bytes(lds);
+    RC_CHECK_HIP(ctx, rc_spec_allow_lds(reinterpret_cast<const void *>(k_spectrum_counts), bytes));
+    const size_t per_block = (size_t)RC_SPEC_WAVES * 64 * 4;
+    const unsigned G = (unsigned)std::min<size_t>(RC_SPEC_MAX_BLOCKS, (n + per_block - 1) / per_block);
+    hipLaunchKernelGGL(k_spectrum_counts, dim3(G), dim3(RC_SPEC_THREADS), bytes, st, d_cnt, n, max_bin, lds, d_out);
+    RC_CHECK_HIP(ctx, hipGetLastError());
+    return RC_OK;
+}
+
+// the spectrum of the context's table into host arrays freq[max_bin + 1], st[4]
+int rc_table_spectrum_scan(rc_ctx *ctx, uint32_t max_bin, uint64_t *freq, uint64_t *st)
+{
+    const size_t words = (size_t)max_bin + 1 + 4;
+    rc_dev_tmp b_out;
+    RC_CHECK_HIP(ctx, b_out.alloc(words * 8));
+    RC_CHECK_HIP(ctx, hipMemsetAsync(b_out.p, 0, words * 8, ctx->stream));
+    const size_t nb = ctx->nb_alloc;
+    if (nb) {
+        const uint32_t lds = rc_spec_lds_bins(max_bin);
+        const size_t bytes = rc_spec_lds_bytes(lds);
+        RC_CHECK_HIP(ctx, rc_spec_allow_lds(reinterpret_cast<const void *>(k_spectrum_table), bytes));
+        const size_t per_block = (size_t)RC_SPEC_WAVES * 64 * RC_SPEC_UNROLL;
+        const unsigned G = (unsigned)std::min<size_t>(RC_SPEC_MAX_BLOCKS, (nb + per_block - 1) / per_block);
+        hipLaunchKernelGGL(k_spectrum_table, dim3(G), dim3(RC_SPEC_THREADS), bytes, ctx->stream, rc_view(ctx), max_bin, lds,
+                           b_out.as<unsigned long long>());
+        RC_CHECK_HIP(ctx, hipGetLastError());
+    }
+    RC_CHECK_HIP(ctx, hipMemcpyAsync(freq, b_out.p, ((size_t)max_bin + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RC_CHECK_HIP(ctx, hipMemcpyAsync(st, b_out.as<unsigned long long>() + (size_t)max_bin + 1, 32, hipMemcpyDeviceToHost, ctx->stream));
+    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RC_OK;
+}
+
 __global__ void k_dump_order_keys(const uint64_t *__restrict__ codes, size_t n, uint64_t *__restrict__ keys)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1276,6 +1456,7 @@ int rc_count_begin(rc_ctx *ctx)
 {
     rc_count_release(ctx);
     rc_kept_release(ctx);
+    ctx->spec_counted.clear();
     ctx->cnt_active = true;
     return RC_OK;
 }
@@ -1350,6 +1531,13 @@ int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers)
     rc_dev_tmp b_hist, b_cursor;
     RC_CHECK_HIP(ctx, b_hist.alloc(64 * 8));
     RC_CHECK_HIP(ctx, b_cursor.alloc(8));
+    // rc_table_count_spectrum: every slice's run-length counts, before the min_count filter, into one device array
+    const uint32_t spec_bin = ctx->spec_arm;
+    rc_dev_tmp b_spec;
+    if (spec_bin) {
+        RC_CHECK_HIP(ctx, b_spec.alloc(((size_t)spec_bin + 5) * 8));
+        RC_CHECK_HIP(ctx, hipMemsetAsync(b_spec.p, 0, ((size_t)spec_bin + 5) * 8, ctx->stream));
+    }
     RC_CHECK_HIP(ctx, hipMemsetAsync(b_hist.p, 0, 64 * 8, ctx->stream));
     for (const auto &a : ctx->cnt_arenas) {
         const unsigned G = (unsigned)((a.bytes + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
@@ -1426,6 +1614,10 @@ int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers)
             t_rle += now() - tp;
             if (runs == 0) continue;
             tp = now();
+            if (spec_bin) {
+                const int rs = rc_launch_spectrum_counts(ctx, ctx->stream, cnt, runs, spec_bin, b_spec.as<unsigned long long>());
+                if (rs) return rs;
+            }
             hipLaunchKernelGGL(k_flag_keep, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, ctx->stream, keys, cnt, runs, min_count, keep);
             // the kept keys land in keys_s (free again) and are copied out; their counts go through a second select into the
             // same buffer and from there, clamped to int32, to their place
@@ -1467,6 +1659,12 @@ int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers)
             total_kept += nsel;
         }
         RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    if (spec_bin) {
+        std::vector<uint64_t> f((size_t)spec_bin + 5);
+        RC_CHECK_HIP(ctx, hipMemcpyAsync(f.data(), b_spec.p, f.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->spec_counted = std::move(f);
     }
     if (!b_allk.p) {  // nothing kept: the build still wants its two arrays
         RC_CHECK_HIP(ctx, b_allk.alloc(8));
@@ -1619,7 +1817,7 @@ int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers)
         for (int g = 0; g < n; ++g) slice_total[p] += (size_t)hist[(size_t)g][p];
     // per owner: the scratch of its largest slice; per GPU: a staging buffer for the keys it emits for someone else
     struct Owner {
-        rc_dev_tmp pool, allk, allc;
+        rc_dev_tmp pool, allk, allc, spec;
         size_t max_slice = 0, tmp_bytes = 0, kept = 0, cap = 0;
         size_t o_keys_s = 0, o_cnt = 0, o_keep = 0, o_runs = 0, o_tmp = 0;
     };
@@ -1627,6 +1825,7 @@ int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers)
     std::vector<rc_dev_tmp> stage((size_t)n), cursor((size_t)n);
     std::vector<size_t> stage_each((size_t)n, 0);
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const uint32_t spec_bin = c0->spec_arm;
     for (int g = 0; g < n; ++g) {
         Owner &O = own[(size_t)g];
         size_t max_emit = 0;
@@ -1655,6 +1854,10 @@ int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers)
         O.o_runs = O.o_keep + up(O.max_slice);
         O.o_tmp = O.o_runs + 256;
         RC_SH_HIP(O.pool.alloc(O.o_tmp + up(O.tmp_bytes)), "hipMalloc");
+        if (spec_bin) {  // (rc_table_count_spectrum on ctxs[0]: every owner sums the spectrum of its slices)
+            RC_SH_HIP(O.spec.alloc(((size_t)spec_bin + 5) * 8), "hipMalloc");
+            RC_SH_HIP(hipMemsetAsync(O.spec.p, 0, ((size_t)spec_bin + 5) * 8, cs[g]->stream), "hipMemsetAsync");
+        }
     }
     // rounds: in round r GPU o owns slice r n + o
     struct Piece {
@@ -1732,6 +1935,10 @@ int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers)
                 } else if (phase == 1) {
                     RC_SH_HIP(hipStreamSynchronize(st), "hipStreamSynchronize");
                     if (runs[(size_t)o] == 0) continue;
+                    if (spec_bin) {
+                        const int rs = rc_launch_spectrum_counts(c0, st, cnt, runs[(size_t)o], spec_bin, O.spec.as<unsigned long long>());
+                        if (rs) return rs;
+                    }
                     hipLaunchKernelGGL(k_flag_keep, dim3((unsigned)((runs[(size_t)o] + 255) / 256)), dim3(256), 0, st, keys, cnt, runs[(size_t)o], min_count, keep);
                     RC_SH_HIP(rocprim::select(tmp, t1, keys, keep, keys_s, d_runs, runs[(size_t)o], st), "select");
                     RC_SH_HIP(hipMemcpyAsync(&nsel[(size_t)o], d_runs, sizeof(size_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
@@ -1770,6 +1977,20 @@ int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers)
             RC_SH_HIP(hipSetDevice(cs[o]->device), "hipSetDevice");
             RC_SH_HIP(hipStreamSynchronize(cs[o]->stream), "hipStreamSynchronize");
         }
+    }
+    if (spec_bin) {  // every owner's few KB back to the host, summed (the slices are disjoint in key space)
+        std::vector<uint64_t> sum((size_t)spec_bin + 5, 0), f((size_t)spec_bin + 5);
+        for (int g = 0; g < n; ++g) {
+            if (!own[(size_t)g].spec.p) continue;
+            RC_SH_HIP(hipSetDevice(cs[g]->device), "hipSetDevice");
+            RC_SH_HIP(hipMemcpyAsync(f.data(), own[(size_t)g].spec.p, f.size() * 8, hipMemcpyDeviceToHost, cs[g]->stream), "hipMemcpyAsync");
+            RC_SH_HIP(hipStreamSynchronize(cs[g]->stream), "hipStreamSynchronize");
+            const size_t mc = (size_t)spec_bin + 4;  // (max_count: a maximum, the rest sums)
+            for (size_t i = 0; i < mc; ++i) sum[i] += f[i];
+            sum[mc] = std::max(sum[mc], f[mc]);
+            own[(size_t)g].spec.reset();
+        }
+        c0->spec_counted = std::move(sum);
     }
     // the kept entries, slice after slice, on cs[0]
     size_t total_kept = 0;
