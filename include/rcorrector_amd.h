@@ -159,6 +159,35 @@ int rc_table_count_spectrum(rc_ctx *ctx, uint32_t max_bin);
  * stats may be NULL. */
 int rc_table_spectrum(rc_ctx *ctx, int source, uint64_t *freq, uint32_t max_bin, rc_spectrum_stats *stats);
 
+/* ---- recount session: the k-mer spectrum of reads AFTER correction, and a census of the k-mers the table does not hold ------
+ * A second, read-only use of the k-mer counter.  Between rc_recount_begin and rc_recount_finish the session collects arenas of
+ * reads (NUL-separated, each arena < 2^32 bytes) in HBM, one byte per base; finish counts them by the counter's rules -- canonical
+ * k-mers at the context's k, windows holding a letter outside ACGT or crossing a NUL skipped, full 32-bit counts -- and probes
+ * every distinct k-mer in the context's table.  freq is laid out as rc_table_spectrum documents (freq[0] = 0, last bin = "at
+ * least"), with the max_bin given to begin (1 .. 2^28).  The session builds no table and never touches the one that is there
+ * (rc_table_digest stays), releases and reorders no kept arena, leaves an armed or stored counted spectrum alone, and gives
+ * the same answer in one pass as in several (RC_COUNT_MEM_MB).  RC_STATUS_STATE: begin / add / finish without a table, add /
+ * finish without begin, begin while a session of either kind is open, rc_table_count_begin while this one is; RC_STATUS_ARG: a
+ * bad max_bin.  finish, an error in add or finish, and rc_destroy end the session and leave nothing of it allocated.
+ * No reference counterpart: there one runs Jellyfish over the corrected files. */
+typedef struct {
+    rc_spectrum_stats all;                  /* distinct, total, unique, max_count of the recounted k-mers */
+    uint64_t absent_distinct, absent_total; /* of those, the k-mers the context's table does not hold (GetCount 0, Store.h:59-66):
+                                               the number of distinct ones, and the sum of their counts */
+} rc_recount_stats;
+int rc_recount_begin(rc_ctx *ctx, uint32_t max_bin);
+/* a host arena / an arena already in HBM (what rc_correct_device has corrected in place: the caller's memory); copied, the
+ * caller's buffer is its own again on return.  No reference counterpart. */
+int rc_recount_add(rc_ctx *ctx, const char *seq, size_t nbytes);
+int rc_recount_add_device(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes);
+/* on != 0 (default off): while a session is open on ctx, every batch that completes on it -- rc_correct_batch, rc_wait,
+ * rc_wait_packed, rc_wait_resident, the batches of slots that run in lanes included -- appends its corrected byte arena to the
+ * session, device to device on the batch's own stream, before the wait returns and the slot can be reused; each batch once.
+ * Without a session, or with on == 0, those calls do exactly what they do without this one.  No reference counterpart. */
+int rc_recount_follow(rc_ctx *ctx, int on);
+/* freq[max_bin + 1] (begin's max_bin); stats may be NULL.  No reference counterpart. */
+int rc_recount_finish(rc_ctx *ctx, uint64_t *freq, rc_recount_stats *stats);
+
 /* ---- run parameters (globals of main.cpp:17-30) ----------------------------------------------- */
 /* replaces main.cpp:310-358 (ERROR_RATE estimation).  Uses the entries parsed by the last
  * rc_table_load_jfdump() in file order -- or, for a table that was counted here or built from

@@ -16,6 +16,7 @@ ABI_SYMBOLS = [
     "rc_table_count_keep", "rc_table_count_arenas", "rc_table_count_release", "rc_table_count_park", "rc_table_count_finish_sharded", "rc_submit_resident", "rc_wait_resident",
     "rc_table_count_reads_device", "rc_table_write_jfdump", "rc_table_share", "rc_table_replicate", "rc_table_replicate_async", "rc_table_lookup", "rc_table_export", "rc_table_digest", "rc_table_layout", "rc_table_stats",
     "rc_table_count_spectrum", "rc_table_spectrum",
+    "rc_recount_begin", "rc_recount_add", "rc_recount_add_device", "rc_recount_follow", "rc_recount_finish",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
@@ -69,6 +70,10 @@ class _ResidentBatch(C.Structure):
 
 class _SpectrumStats(C.Structure):
     _fields_ = [("distinct", C.c_uint64), ("total", C.c_uint64), ("unique", C.c_uint64), ("max_count", C.c_uint64)]
+
+
+class _RecountStats(C.Structure):
+    _fields_ = [("all", _SpectrumStats), ("absent_distinct", C.c_uint64), ("absent_total", C.c_uint64)]
 
 
 class _DeviceBatch(C.Structure):
@@ -138,6 +143,11 @@ def load_library():
     L.rc_table_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rc_table_count_spectrum.argtypes = [vp, C.c_uint32]
     L.rc_table_spectrum.argtypes = [vp, C.c_int, vp, C.c_uint32, C.POINTER(_SpectrumStats)]
+    L.rc_recount_begin.argtypes = [vp, C.c_uint32]
+    L.rc_recount_add.argtypes = [vp, vp, C.c_size_t]
+    L.rc_recount_add_device.argtypes = [vp, vp, C.c_size_t]
+    L.rc_recount_follow.argtypes = [vp, C.c_int]
+    L.rc_recount_finish.argtypes = [vp, vp, C.POINTER(_RecountStats)]
     L.rc_estimate_error_rate.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.rc_bad_quality_from_hist.restype = C.c_char
     L.rc_bad_quality_from_hist.argtypes = [vp, vp, C.c_int32]
@@ -353,6 +363,37 @@ class Context:
         st = _SpectrumStats()
         self._ck(self._L.rc_table_spectrum(self._h, src, freq.ctypes.data, int(max_bin), C.byref(st)))
         return freq, {"distinct": st.distinct, "total": st.total, "unique": st.unique, "max_count": st.max_count}
+
+    # ---- recount session: the spectrum of reads after correction, and the k-mers the table does not hold ----
+    def recount_begin(self, max_bin=10000):
+        """rc_recount_begin: opens a counting session that builds no table and leaves the table, the kept arenas and a
+        counted spectrum alone; recount_finish bins into max_bin + 1 bins (the last one: counts >= max_bin)."""
+        self._ck(self._L.rc_recount_begin(self._h, int(max_bin)))
+        self._recount_bin = int(max_bin)
+
+    def recount_add(self, arena):
+        """arena: bytes / uint8 array of NUL-separated reads in host memory"""
+        a = np.frombuffer(arena, dtype=np.uint8) if isinstance(arena, (bytes, bytearray)) else np.ascontiguousarray(arena, dtype=np.uint8)
+        self._ck(self._L.rc_recount_add(self._h, a.ctypes.data, a.size))
+
+    def recount_add_device(self, d_seq, nbytes):
+        """an arena in HBM, e.g. what correct_device has corrected in place"""
+        self._ck(self._L.rc_recount_add_device(self._h, _ptr(d_seq), nbytes))
+
+    def recount_follow(self, on=True):
+        """rc_recount_follow: while a session is open, every batch that completes on this context (correct_batch, wait,
+        wait_packed, wait_resident) leaves its corrected arena with the session, device to device."""
+        self._ck(self._L.rc_recount_follow(self._h, 1 if on else 0))
+
+    def recount_finish(self):
+        """rc_recount_finish: (uint64 array freq[max_bin + 1], {"distinct", "total", "unique", "max_count", "absent_distinct",
+        "absent_total"}) of the k-mers of everything added since recount_begin; absent = not in this context's table."""
+        freq = np.zeros(getattr(self, "_recount_bin", 0) + 1, dtype=np.uint64)
+        st = _RecountStats()
+        self._ck(self._L.rc_recount_finish(self._h, freq.ctypes.data, C.byref(st)))
+        a = st.all
+        return freq, {"distinct": a.distinct, "total": a.total, "unique": a.unique, "max_count": a.max_count,
+                      "absent_distinct": st.absent_distinct, "absent_total": st.absent_total}
 
     # ---- run parameters ----
     def estimate_error_rate(self, wk=0.95):

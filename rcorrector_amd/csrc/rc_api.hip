@@ -121,6 +121,7 @@ rc_ctx *rc_slot_lane(rc_ctx *ctx, int slot, bool create, bool refresh)
             return nullptr;
         }
         ln->is_lane = true;
+        ln->lane_parent = ctx;
     }
     if (refresh) {  // plain assignments: the table (borrowed, as rc_table_share lends it), the parameters, the mode, the kept arenas
         ln->d_buckets = ctx->d_buckets;
@@ -262,6 +263,7 @@ void rc_destroy(rc_ctx *c)
     for (auto &a : ctx->cnt_chunks)
         if (a.p) (void)hipFree(a.p);
     rc_kept_release(ctx);
+    rc_recount_release(ctx);
     rc_table_release(ctx);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

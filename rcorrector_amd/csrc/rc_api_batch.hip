@@ -417,7 +417,7 @@ static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t)
         }
     }
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RC_OK;
+    return rc_recount_take(ctx, d_seq, nbytes);  // (rc_recount_follow: the traced entry point's batches complete here)
 }
 
 // ---- asynchronous host-buffer path ---------------------------------------------------------------
@@ -537,6 +537,7 @@ int rc_submit(rc_ctx *c, const rc_batch *b, int slot)
         return RC_OK;
     }
     const size_t nbytes = sl.bytes1 + sl.bytes2, total = sl.total_reads;
+    sl.arena_bytes = nbytes;
     if (nbytes >= (1ull << 32) || total >= (1ull << 32)) {
         rc_set_error(ctx, "submit: batch too large (split it)");
         return RC_ERR_ARG;
@@ -675,6 +676,7 @@ int rc_wait(rc_ctx *c, int slot)
     if (sl.b.n == 0) return RC_OK;
     RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     RC_CHECK_HIP(ctx, hipEventSynchronize(sl.e_done));
+    if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;  // (rc_recount_follow: before the slot can be reused)
     const size_t total = sl.total_reads;
     if (!sl.seq_pinned) {
         memcpy(sl.b.seq, sl.p_seq.p, sl.bytes1);

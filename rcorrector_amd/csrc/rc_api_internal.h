@@ -42,6 +42,7 @@ struct rc_slot {
     bool busy = false;
     rc_batch b;                      // the caller's descriptor (its buffers stay valid until rc_wait)
     size_t total_reads = 0, bytes1 = 0, bytes2 = 0;
+    size_t arena_bytes = 0;          // bytes of the batch's arena in d_seq (what rc_recount_follow takes when the batch completes)
     bool seq_pinned = false, res_pinned = false;  // the caller's buffers are page-locked: DMA straight from / to them
     rc_hbuf p_seq, p_qual, p_off, p_res;           // pinned staging (seq/qual only when the caller's are pageable)
     rc_dbuf d_seq, d_qual, d_off, d_res;
@@ -70,4 +71,8 @@ int rc_slots_init(rc_ctx *ctx);
 rc_ctx *rc_slot_lane(rc_ctx *ctx, int slot, bool create, bool refresh);
 // the lane's error text and summary counters seen through the parent
 void rc_lane_error(rc_ctx *ctx, const rc_ctx *lane);
+// rc_api_table.hip
+// rc_recount_follow: a batch has completed in ctx (a context or one of its slot lanes) and its corrected arena lies in d_seq --
+// appended to the open session of the context the batch was submitted to, on ctx's own stream; nothing without a session
+int rc_recount_take(rc_ctx *ctx, const void *d_seq, size_t nbytes);
 }

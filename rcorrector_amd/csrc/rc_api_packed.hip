@@ -119,6 +119,7 @@ int rc_submit_packed(rc_ctx *c, rc_packed_batch *b, int slot)
     sl.b.n = b->n;
     sl.total_reads = total;
     const size_t n_words = (nbytes + 15) / 16, qb = (nbytes + 7) / 8, n_exc = b->n_exc;
+    sl.arena_bytes = nbytes;
     const uint32_t cap = (uint32_t)b->fix_cap;
     // device memory: the packed arena, the byte arena it expands into, qualities, offsets, results, exceptions, fixes
     if ((rc = rc_dbuf_reserve(ctx, &sl.d_packed, n_words * 4 + 64))) return rc;
@@ -262,6 +263,8 @@ int rc_wait_packed(rc_ctx *c, int slot)
         rc_set_error(ctx, "wait_packed: %u substitutions, room for %u (fix_cap)", n_fix, cap);
         return RC_ERR_NOSPACE;
     }
+    // rc_recount_follow: before the slot can be reused (a batch that did not fit its fix list comes again and is taken then)
+    if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;
     const uint32_t *o_pos = (const uint32_t *)sl.p_fix.p;
     const uint8_t *o_chr = (const uint8_t *)sl.p_fix.p + (size_t)cap * 4;
     if (!sl.res_pinned) {
@@ -351,6 +354,7 @@ int rc_submit_resident(rc_ctx *c, rc_resident_batch *b, int slot)
     sl.total_reads = total;
     const size_t qb = (nbytes + 7) / 8;
     const uint32_t cap = (uint32_t)b->fix_cap;
+    sl.arena_bytes = nbytes;
     if ((rc = rc_dbuf_reserve(ctx, &sl.d_seq, ((nbytes + 15) & ~(size_t)15) + 64))) return rc;
     if ((rc = rc_dbuf_reserve(ctx, &sl.d_qual, (b->qual_bits ? qb : nbytes) + 64))) return rc;
     if ((rc = rc_dbuf_reserve(ctx, &sl.d_off, (total + 1) * 4))) return rc;
@@ -465,6 +469,8 @@ int rc_wait_resident(rc_ctx *c, int slot)
         rc_set_error(ctx, "wait_resident: %u substitutions, room for %u (fix_cap)", n_fix, cap);
         return RC_ERR_NOSPACE;
     }
+    // rc_recount_follow: before the slot can be reused (a batch that did not fit its fix list comes again and is taken then)
+    if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;
     if (!sl.res_pinned) {
         const int32_t *r = (const int32_t *)sl.p_res.p;
         memcpy(b->ret, r, total * 4);

@@ -685,6 +685,106 @@ int rc_table_spectrum(rc_ctx *ctx, int source, uint64_t *freq, uint32_t max_bin,
     return RC_OK;
 }
 
+// ---- recount session (include/rcorrector_amd.h) ------------------------------------------------------------------------------
+int rc_recount_begin(rc_ctx *ctx, uint32_t max_bin)
+{
+    if (!ctx) return RC_ERR_ARG;
+    if (max_bin < 1 || max_bin > RC_SPEC_MAX_BIN) {
+        rc_set_error(ctx, "recount_begin: max_bin must be 1..%u", RC_SPEC_MAX_BIN);
+        return RC_ERR_ARG;
+    }
+    if (!ctx->d_buckets) {
+        rc_set_error(ctx, "recount_begin: no k-mer table loaded");
+        return RC_ERR_STATE;
+    }
+    if (ctx->cnt_active) {
+        rc_set_error(ctx, "recount_begin: a counting session is open (rc_table_count_finish or rc_table_count_park it first)");
+        return RC_ERR_STATE;
+    }
+    if (ctx->rec_active) {
+        rc_set_error(ctx, "recount_begin: a recount session is open already (rc_recount_finish it first)");
+        return RC_ERR_STATE;
+    }
+    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return rc_recount_begin_session(ctx, max_bin);
+}
+
+static int recount_open(rc_ctx *ctx, const char *what)
+{
+    if (!ctx->rec_active) {
+        rc_set_error(ctx, "%s: call rc_recount_begin first", what);
+        return RC_ERR_STATE;
+    }
+    if (!ctx->d_buckets) {
+        rc_set_error(ctx, "%s: no k-mer table loaded", what);
+        return RC_ERR_STATE;
+    }
+    return RC_OK;
+}
+
+int rc_recount_add(rc_ctx *ctx, const char *seq, size_t nbytes)
+{
+    if (!ctx || (nbytes && !seq)) return RC_ERR_ARG;
+    if (const int rc = recount_open(ctx, "recount_add")) return rc;
+    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return rc_recount_append(ctx, reinterpret_cast<const uint8_t *>(seq), nbytes, false, ctx->stream);
+}
+
+int rc_recount_add_device(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes)
+{
+    if (!ctx || (nbytes && !d_seq)) return RC_ERR_ARG;
+    if (const int rc = recount_open(ctx, "recount_add_device")) return rc;
+    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return rc_recount_append(ctx, d_seq, nbytes, true, ctx->stream);
+}
+
+int rc_recount_follow(rc_ctx *ctx, int on)
+{
+    if (!ctx) return RC_ERR_ARG;
+    ctx->rec_follow = on != 0;
+    return RC_OK;
+}
+
+int rc_recount_take(rc_ctx *ctx, const void *d_seq, size_t nbytes)
+{
+    rc_ctx *home = ctx->is_lane && ctx->lane_parent ? ctx->lane_parent : ctx;
+    if (!home->rec_active || !home->rec_follow || !nbytes) return RC_OK;
+    const int rc = rc_recount_append(home, static_cast<const uint8_t *>(d_seq), nbytes, true, ctx->stream);
+    if (rc && home != ctx) rc_lane_error(ctx, home);  // (the wait reports through the lane)
+    return rc;
+}
+
+int rc_recount_finish(rc_ctx *ctx, uint64_t *freq, rc_recount_stats *stats)
+{
+    if (!ctx) return RC_ERR_ARG;
+    if (const int rc = recount_open(ctx, "recount_finish")) {
+        if (ctx->rec_active) rc_recount_release(ctx);  // (the table went away under the session)
+        return rc;
+    }
+    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (!freq) {
+        rc_recount_release(ctx);
+        rc_set_error(ctx, "recount_finish: freq is NULL");
+        return RC_ERR_ARG;
+    }
+    const uint32_t max_bin = ctx->rec_bin;
+    std::vector<uint64_t> out;
+    const int rc = rc_recount_finish_session(ctx, &out);
+    if (rc) return rc;
+    std::copy(out.begin(), out.begin() + max_bin + 1, freq);
+    freq[0] = 0;
+    if (stats) {
+        const uint64_t *st = out.data() + max_bin + 1;
+        stats->all.distinct = st[0];
+        stats->all.total = st[1];
+        stats->all.unique = st[2];
+        stats->all.max_count = st[3];
+        stats->absent_distinct = st[4];
+        stats->absent_total = st[5];
+    }
+    return RC_OK;
+}
+
 int rc_table_layout(const rc_ctx *ctx)
 {
     if (!ctx) return RC_ERR_ARG;

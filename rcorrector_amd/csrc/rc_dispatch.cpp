@@ -339,6 +339,24 @@ static void raise_lane_limit(Run &R, const char *why)
     if (g_timing) fprintf(stderr, "[rc timing] %s: %d batches in flight per GPU from now on\n", why, R.lane_limit);
 }
 
+// -histo-after with several GPUs: the corrected bases of one file's share of a batch, as the host holds them -- the byte arena,
+// or (a resident batch: the fixes were applied to the text) the sequence lines gathered into one -- to the recount session
+static int recount_feed(rc_ctx *c0, const Arena &A)
+{
+    const size_t n = A.n();
+    if (n == 0) return 0;
+    if (!A.seq_in_text) return rc_recount_add(c0, A.seq.data(), A.off[n]);
+    std::vector<char> buf;
+    buf.reserve(A.off[n]);
+    for (size_t r = 0; r < n; ++r) {
+        uint32_t len = 0;
+        const char *s = A.line(r, 1, &len);
+        buf.insert(buf.end(), s, s + len);
+        buf.push_back(0);
+    }
+    return rc_recount_add(c0, buf.data(), buf.size());
+}
+
 static void worker_body(Run &R, int wk)
 {
     std::vector<ReadFile> &files = R.files, &mates = R.mates;
@@ -620,6 +638,11 @@ static void worker_body(Run &R, int wk)
             }
             if (!rc) rc = rc_wait(ctx[g], slot);
         }
+        bool fed = true;
+        if (!rc && R.recount_host) {
+            fed = !recount_feed(ctx[0], j->a) && (j->mode != 1 || !recount_feed(ctx[0], j->b));
+            if (!fed) rc = RC_STATUS_STATE;
+        }
         const double tf0 = now_s();
         if (!rc) format_job(R, *j);
         const double tf1 = now_s();
@@ -629,7 +652,7 @@ static void worker_body(Run &R, int wk)
             g_t_format += tf1 - tf0;
             g_t_pack += tp1 - tp0;
             j->rc = rc;
-            if (rc) j->err = rc_last_error(ctx[g]);
+            if (rc) j->err = rc_last_error(fed ? ctx[g] : ctx[0]);
             j->done = true;
             --R.active[(size_t)g];
             // a batch that took the GPU longer than twice what its output takes to write (15 GB/s, 2.2 output bytes per base):

@@ -32,6 +32,7 @@ struct Run {
     bool resident = false;  // one pass: the batches are `kept`, their bases in HBM
     bool numa_on = true, shared_gpu = false;
     char bad_q = 0;
+    bool recount_host = false;  // -histo-after with several GPUs: the workers hand every corrected batch's bases to ctx[0]'s recount session
     std::vector<ReadFile> files, mates;
     std::vector<rc_ctx *> ctx;                // one per GPU (the table is replicated)
     std::unique_ptr<std::mutex[]> submit_mu;  // rc_submit calls on one context are serialised

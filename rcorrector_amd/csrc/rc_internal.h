@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <mutex>
 #include <vector>
 
 #include "rc_correct_core.h"
@@ -124,6 +125,15 @@ struct rc_ctx {
     // since the last count_begin
     uint32_t spec_arm = 0;
     std::vector<uint64_t> spec_counted;
+    // recount session (rc_recount_begin): a second counting session that builds no table -- its arenas in chunks of its own
+    // (the counter's and the kept arenas are never touched), the bound its spectrum is binned to, and whether the batches
+    // that complete on this context (its slot lanes included: lane_parent) append their corrected arena (rc_recount_follow)
+    std::vector<rc_dbuf> rec_arenas, rec_chunks;
+    size_t rec_chunk_used = 0, rec_total = 0;
+    bool rec_active = false, rec_follow = false;
+    uint32_t rec_bin = 0;
+    std::mutex rec_mutex;
+    rc_ctx *lane_parent = nullptr;  // a slot lane: the context whose slots it serves
 
     // batch scratch
     rc_dbuf counts;   // int32 per arena byte
@@ -196,6 +206,12 @@ int rc_launch_export(rc_ctx *ctx, uint64_t *d_codes, int32_t *d_counts, unsigned
 // counts added to d_out (freq[max_bin + 1], then the four statistics; zeroed by the caller) on stream st
 int rc_table_spectrum_scan(rc_ctx *ctx, uint32_t max_bin, uint64_t *freq, uint64_t *st);
 int rc_launch_spectrum_counts(rc_ctx *ctx, hipStream_t st, const uint32_t *d_cnt, size_t n, uint32_t max_bin, unsigned long long *d_out);
+// recount session: begin / append a copy of an arena (on stream st; complete on return) / the passes and the census kernel
+// (out: freq[rec_bin + 1], distinct, total, unique, max_count, absent_distinct, absent_total) / release (also on every error)
+int rc_recount_begin_session(rc_ctx *ctx, uint32_t max_bin);
+int rc_recount_append(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_device, hipStream_t st);
+int rc_recount_finish_session(rc_ctx *ctx, std::vector<uint64_t> *out);
+void rc_recount_release(rc_ctx *ctx);
 int rc_table_entries_in_dump_order(rc_ctx *ctx, std::vector<uint64_t> *codes, std::vector<int32_t> *counts);
 int rc_error_rate_candidates(rc_ctx *ctx, const uint64_t *d_codes, size_t n, bool by_hash, size_t want, std::vector<uint64_t> *vals);
 int rc_table_codes_device(rc_ctx *ctx, uint64_t **d_codes, size_t *n);

@@ -21,6 +21,8 @@
 // -write-dump FILE keeps the k-mer table as jellyfish-dump text; without -c the k-mers are counted here.
 // -histo FILE writes the k-mer count spectrum as `jellyfish histo` prints it (-histo-max: its last bin): without -c the
 // spectrum of every k-mer counted, singletons included; with -c that of the dump's entries.
+// -histo-after FILE writes the spectrum of the CORRECTED reads in the same format (a recount session, rcorrector_amd.h:
+// rc_recount_begin) and adds one line to stderr: how many of their k-mers the table does not hold.
 #include <fcntl.h>
 #include <malloc.h>
 #include <sys/stat.h>
@@ -58,6 +60,9 @@ static void print_help()
             "\t-histo STRING: also write the k-mer count spectrum (\"<count> <frequency>\" lines, as jellyfish histo prints them):\n"
             "\t\twithout -c of every k-mer counted, count 1 included; with -c of the dump's k-mers\n"
             "\t-histo-max INT: the spectrum's last bin, which holds the k-mers counted at least that often (default: 10000)\n"
+            "\t-histo-after STRING: also write the k-mer count spectrum of the corrected reads (same format, -histo-max bounds it too) and\n"
+            "\t\treport how many of their k-mers the table does not hold; the corrected bases stay in GPU memory until the end of the run\n"
+            "\t\t(one byte per base); with -gpus above 1 they are counted on the first GPU, from the corrected text the host holds\n"
             "\t-verbose-iter INT: threshold iterations recorded per read for -verbose (default: 64)\n");
 }
 
@@ -70,7 +75,7 @@ int main(int argc, char **argv)
     std::vector<ReadFile> &files = run.files, &mates = run.mates;
     int max_fix_per_k = 4, i;
     double wk = 0.95;
-    const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr;
+    const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr;
     long histo_max = 10000;
     std::string od = "./";
     bool verbose = false;
@@ -124,6 +129,8 @@ int main(int argc, char **argv)
             histo = argv[++i];
         else if (!strcmp("-histo-max", argv[i]))
             histo_max = atol(argv[++i]);
+        else if (!strcmp("-histo-after", argv[i]))
+            histo_after = argv[++i];
         else if (!strcmp("-packed", argv[i]))
             g_packed = true;
         else if (!strcmp("-h", argv[i])) {
@@ -139,7 +146,7 @@ int main(int argc, char **argv)
     // -verbose carries RC_TRACE_ITER_WORDS x trace-iter words per read through host and device
     // (9 KB per read at the default 64 iterations): small batches, or a real data set needs tens of GB
     if (verbose && batch_reads > (1u << 16)) batch_reads = 1u << 16;
-    if (histo && (histo_max < 1 || histo_max > (1l << 28))) die("rcorrector: -histo-max must be 1..%ld\n", 1l << 28);
+    if ((histo || histo_after) && (histo_max < 1 || histo_max > (1l << 28))) die("rcorrector: -histo-max must be 1..%ld\n", 1l << 28);
     if (gpus < 1) gpus = 1;
     if (inflight < 1) inflight = 1;
     if (inflight > 8) inflight = 8;
@@ -424,6 +431,50 @@ int main(int argc, char **argv)
     const double t_setup = now_s();
     stamp("start-up done");
 
+    // -histo-after: a recount session on the first GPU's context.  One GPU: every batch that completes leaves its corrected
+    // arena with the session, device to device (rc_recount_follow); several: the workers hand over the corrected text's bases.
+    if (histo_after) {
+        // the bases stay in HBM until the finish, next to its sort scratch: stop here rather than half-way if they will not fit
+        uint64_t bases = 0;
+        bool known = true;
+        if (resident) {
+            for (int c = 0; c < nctx; ++c) {
+                size_t na = 0;
+                if (rc_table_count_arenas(ctx[c], &na, nullptr, 0)) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+                std::vector<uint64_t> ab(na);
+                if (na && rc_table_count_arenas(ctx[c], &na, ab.data(), na)) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+                for (uint64_t b : ab) bases += b;
+            }
+        } else {
+            for (size_t fi = 0; fi < files.size(); ++fi)
+                for (const ReadFile *f : {(const ReadFile *)&files[fi], files[fi].paired ? (const ReadFile *)&mates[fi] : (const ReadFile *)nullptr}) {
+                    if (!f) continue;
+                    struct stat st;
+                    if (stat(f->path.c_str(), &st) != 0 || !S_ISREG(st.st_mode)) {
+                        known = false;  // (a pipe: its size is anybody's guess, the session says so if it runs out)
+                        continue;
+                    }
+                    // bases per byte of file: half of a FASTQ file, all of a FASTA file at most; deflated FASTQ is a fifth to a quarter of its text
+                    const uint64_t text = f->src.is_gz ? (uint64_t)st.st_size * 5 : (uint64_t)st.st_size;
+                    bases += f->fastq ? text / 2 + text / 16 : text;
+                }
+        }
+        uint64_t hbm_free = 0;
+        if (rc_device_memory(ctx[0], &hbm_free, nullptr)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+        if (const char *hf = getenv("RC_HBM_FREE_MB")) hbm_free = (uint64_t)atoll(hf) << 20;  // tests: as if this much were free
+        const uint64_t scratch = std::min<uint64_t>(count_mem, bases * 46);  // (the passes' scratch: rc_table.hip, 40 bytes per k-mer occurrence + 15 %)
+        const uint64_t need = bases + scratch + ((uint64_t)256 << 20);
+        if ((known || bases) && need > hbm_free)
+            die("rcorrector: -histo-after keeps the corrected bases in GPU memory until the end of the run: about %llu MB with the counting scratch, "
+                "%llu MB are free (lower RC_COUNT_MEM_MB, or run without -histo-after)\n", (unsigned long long)(need >> 20), (unsigned long long)(hbm_free >> 20));
+        if (rc_recount_begin(ctx[0], (uint32_t)histo_max)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+        if (gpus == 1) {
+            if (rc_recount_follow(ctx[0], 1)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+        } else {
+            run.recount_host = true;
+        }
+    }
+
     // pipeline: reader (this thread) -> `inflight` workers per GPU -> writer thread (input order)
     warm.join();
     stamp("batch buffers ready");
@@ -457,6 +508,16 @@ int main(int argc, char **argv)
     if (g_timing)
         fprintf(stderr, "[rc timing] blocked: reader %.2f s (no free slot), workers %.2f s (no batch), writer %.2f s (next batch not done)\n", g_w_reader, g_w_worker, g_w_writer);
     fprintf(stderr, "Processed %llu reads\n\tCorrected %llu bases.\n", (unsigned long long)run.total_reads, (unsigned long long)run.total_cor);
+    if (histo_after) {
+        const double th0 = now_s();
+        std::vector<uint64_t> freq((size_t)histo_max + 1);
+        rc_recount_stats rs;
+        if (rc_recount_finish(ctx[0], freq.data(), &rs)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+        if (!write_histo(histo_after, freq)) die("rcorrector: could not write %s\n", histo_after);
+        if (g_timing) fprintf(stderr, "[rc timing] -histo-after: recount of the corrected reads %.2f s\n", now_s() - th0);
+        fprintf(stderr, "Corrected reads: %llu distinct k-mers, %llu seen once, %llu not in the table (%llu occurrences)\n", (unsigned long long)rs.all.distinct,
+                (unsigned long long)rs.all.unique, (unsigned long long)rs.absent_distinct, (unsigned long long)rs.absent_total);
+    }
     stamp("outputs closed, leaving");
     if (getenv("RC_TEARDOWN")) {  // dev: where the time between _exit and the parent's wait goes
         run.pool.clear();

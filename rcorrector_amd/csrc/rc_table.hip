@@ -1454,11 +1454,51 @@ void rc_kept_release(rc_ctx *ctx)
 
 int rc_count_begin(rc_ctx *ctx)
 {
+    if (ctx->rec_active) {
+        rc_set_error(ctx, "count_begin: a recount session is open (rc_recount_finish it first)");
+        return RC_ERR_STATE;
+    }
     rc_count_release(ctx);
     rc_kept_release(ctx);
     ctx->spec_counted.clear();
     ctx->cnt_active = true;
     return RC_OK;
+}
+
+// an arena's place in a session's chunks (behind the last one in the current chunk, 256-byte aligned with 64 bytes of slack, or
+// a new chunk) and its copy there on stream `st`, complete when this returns: the caller's buffer is its own again
+static int rc_arena_keep(rc_ctx *ctx, std::vector<rc_dbuf> &arenas, std::vector<rc_dbuf> &chunks, size_t &chunk_used, size_t &total, const uint8_t *seq,
+                         size_t nbytes, bool from_device, hipStream_t st, const char *what)
+{
+    const size_t need = (nbytes + 64 + 255) & ~(size_t)255, chunk_bytes = (size_t)2 << 30;
+    if (chunks.empty() || chunk_used + need > chunks.back().bytes) {
+        rc_dbuf c;
+        c.bytes = need > chunk_bytes ? need : chunk_bytes;
+        RC_CHECK_HIP(ctx, hipMalloc(&c.p, c.bytes));
+        chunks.push_back(c);
+        chunk_used = 0;
+    }
+    rc_dbuf a;
+    a.p = (char *)chunks.back().p + chunk_used;
+    a.bytes = nbytes;
+    hipError_t e = hipMemcpyAsync(a.p, seq, nbytes, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the caller's buffer is its own again when this returns)
+    if (e != hipSuccess) {
+        rc_set_error(ctx, "%s: copy failed: %s", what, hipGetErrorString(e));
+        return RC_ERR_HIP;
+    }
+    chunk_used += need;
+    arenas.push_back(a);
+    total += nbytes;
+    return RC_OK;
+}
+
+// what a session may keep in HBM
+static size_t rc_count_retain_cap()
+{
+    size_t cap = (size_t)128 << 30;
+    if (const char *e = getenv("RC_COUNT_RETAIN_MB")) cap = (size_t)atoll(e) << 20;
+    return cap;
 }
 
 // keeps a copy of the arena in HBM (from_device: d_seq is device memory, else host memory)
@@ -1473,73 +1513,58 @@ int rc_count_add(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_devic
         rc_set_error(ctx, "count: an arena must be below 2^32 bytes (add it in pieces)");
         return RC_ERR_ARG;
     }
-    size_t cap = (size_t)128 << 30;  // what the counter may keep in HBM
-    if (const char *e = getenv("RC_COUNT_RETAIN_MB")) cap = (size_t)atoll(e) << 20;
+    const size_t cap = rc_count_retain_cap();
     if (ctx->cnt_total + nbytes > cap) {
         rc_set_error(ctx, "count: %zu MB of reads exceed what the k-mer counter keeps in HBM (%zu MB, RC_COUNT_RETAIN_MB): count them with "
                           "jellyfish and pass the dump (-c)", (ctx->cnt_total + nbytes) >> 20, cap >> 20);
         return RC_ERR_NOMEM;
     }
-    // the arena's place: behind the last one in the current chunk (256-byte aligned, 64 bytes of slack), or a new chunk
-    const size_t need = (nbytes + 64 + 255) & ~(size_t)255, chunk_bytes = (size_t)2 << 30;
-    if (ctx->cnt_chunks.empty() || ctx->cnt_chunk_used + need > ctx->cnt_chunks.back().bytes) {
-        rc_dbuf c;
-        c.bytes = need > chunk_bytes ? need : chunk_bytes;
-        RC_CHECK_HIP(ctx, hipMalloc(&c.p, c.bytes));
-        ctx->cnt_chunks.push_back(c);
-        ctx->cnt_chunk_used = 0;
-    }
-    rc_dbuf a;
-    a.p = (char *)ctx->cnt_chunks.back().p + ctx->cnt_chunk_used;
-    a.bytes = nbytes;
-    hipError_t e = hipMemcpyAsync(a.p, seq, nbytes, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (the caller's buffer is its own again when this returns)
-    if (e != hipSuccess) {
-        rc_set_error(ctx, "count_add: copy failed: %s", hipGetErrorString(e));
-        return RC_ERR_HIP;
-    }
-    ctx->cnt_chunk_used += need;
-    ctx->cnt_arenas.push_back(a);
-    ctx->cnt_total += nbytes;
-    return RC_OK;
+    return rc_arena_keep(ctx, ctx->cnt_arenas, ctx->cnt_chunks, ctx->cnt_chunk_used, ctx->cnt_total, seq, nbytes, from_device, ctx->stream, "count_add");
 }
 
-int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers)
+// ---- the pass loop both finishes share (rc_count_finish: the table; rc_recount_finish: the census of a recount session) -----
+// One key slice, sorted and run-length encoded, as a pass hands it to its consumer: `runs` distinct canonical codes in uniq
+// (ascending) with their counts in cnt.  keys_s, keep, d_runs and tmp are the pass's scratch, free for the consumer; all of it
+// is overwritten by the next pass, which the stream orders behind what the consumer queued.
+struct rc_count_pass {
+    uint32_t p, P;
+    const unsigned long long *hist;  // k-mer occurrences per slice
+    unsigned long long occ_total;
+    const uint64_t *uniq;
+    const uint32_t *cnt;
+    size_t runs;
+    uint64_t *keys_s;  // max_slice codes
+    uint8_t *keep;     // max_slice bytes
+    size_t *d_runs;
+    void *tmp;         // rocPRIM scratch: enough for a sort, a run-length encode or a select of max_slice items
+    size_t tmp_bytes;
+};
+// where the passes spent their time (t_sort / t_rle: with RC_COUNT_TIMING's extra synchronisations)
+struct rc_count_times {
+    uint32_t P = 0;
+    double alloc = 0, emit = 0, sort = 0, rle = 0;
+};
+
+// histogram -> P passes over `arenas` (total_bytes of reads): emit slice p's canonical codes -> radix sort -> run-length
+// encode -> consume(pass).  Returns with the stream drained.
+template <class F>
+static int rc_count_passes(rc_ctx *ctx, const std::vector<rc_dbuf> &arenas, size_t total_bytes, bool timing, rc_count_times &T, F &&consume)
 {
-    if (!ctx->cnt_active) {
-        rc_set_error(ctx, "count_finish: call rc_table_count_begin first");
-        return RC_ERR_STATE;
-    }
-    ctx->cnt_active = false;
-    // RC_COUNT_TIMING=1 (dev): where finish() spends its time, on stderr
-    static const bool timing = getenv("RC_COUNT_TIMING") != nullptr;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
-    double t_alloc = 0, t_emit = 0, t_sort = 0, t_rle = 0, t_sel = 0;  // (t_sort / t_rle / t_sel: with RC_COUNT_TIMING's extra synchronisations)
-    struct release_on_exit {
-        rc_ctx *c;
-        ~release_on_exit() { rc_count_release(c); }  // (an error leaves nothing behind; success with cnt_keep has moved the arenas out)
-    } guard{ctx};
     const int k = ctx->k;
     // passes: a pass holds, per k-mer occurrence of its slice, the key (8 B), its sorted copy (8 B), the sort's scratch
     // (~8 B) and the run-length output (8 + 4 + 1 B)
     size_t mem = (size_t)24 << 30;
     if (const char *e = getenv("RC_COUNT_MEM_MB")) mem = (size_t)atoll(e) << 20;
     const double per_occ = 40.0;
-    uint32_t P = (uint32_t)((double)ctx->cnt_total * per_occ * 1.15 / (double)mem) + 1;
+    uint32_t P = (uint32_t)((double)total_bytes * per_occ * 1.15 / (double)mem) + 1;
     if (P > 64) P = 64;
+    T.P = P;
     rc_dev_tmp b_hist, b_cursor;
     RC_CHECK_HIP(ctx, b_hist.alloc(64 * 8));
     RC_CHECK_HIP(ctx, b_cursor.alloc(8));
-    // rc_table_count_spectrum: every slice's run-length counts, before the min_count filter, into one device array
-    const uint32_t spec_bin = ctx->spec_arm;
-    rc_dev_tmp b_spec;
-    if (spec_bin) {
-        RC_CHECK_HIP(ctx, b_spec.alloc(((size_t)spec_bin + 5) * 8));
-        RC_CHECK_HIP(ctx, hipMemsetAsync(b_spec.p, 0, ((size_t)spec_bin + 5) * 8, ctx->stream));
-    }
     RC_CHECK_HIP(ctx, hipMemsetAsync(b_hist.p, 0, 64 * 8, ctx->stream));
-    for (const auto &a : ctx->cnt_arenas) {
+    for (const auto &a : arenas) {
         const unsigned G = (unsigned)((a.bytes + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
         hipLaunchKernelGGL(k_count_scan<0>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, (const uint8_t *)a.p, a.bytes, k, P, 0u,
                            b_hist.as<unsigned long long>(), (uint64_t *)nullptr, (unsigned long long *)nullptr);
@@ -1554,112 +1579,147 @@ int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers)
         rc_set_error(ctx, "count: a pass of %zu k-mer occurrences exceeds 2^32 (lower RC_COUNT_MEM_MB for more passes)", max_slice);
         return RC_ERR_ARG;
     }
+    if (max_slice == 0) return RC_OK;
+    // One allocation holds the passes' scratch.  (Round 3 allocated per pass and concatenated at the end: some forty
+    // hipMalloc / hipFree calls, each a round trip through the kernel driver -- 0.1 s on a quiet host, 0.5 s and more on a
+    // busy one, against 0.2 s for the counting itself.)
+    size_t ts_sort = 0, ts_rle = 0, ts_sel = 0;
+    RC_CHECK_HIP(ctx, rocprim::radix_sort_keys(nullptr, ts_sort, (uint64_t *)nullptr, (uint64_t *)nullptr, max_slice, 0, 2 * k > 64 ? 64 : 2 * k, ctx->stream));
+    RC_CHECK_HIP(ctx, rocprim::run_length_encode(nullptr, ts_rle, (uint64_t *)nullptr, (unsigned int)max_slice, (uint64_t *)nullptr, (uint32_t *)nullptr,
+                                                 (size_t *)nullptr, ctx->stream));
+    RC_CHECK_HIP(ctx, rocprim::select(nullptr, ts_sel, (uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t *)nullptr, (size_t *)nullptr, max_slice, ctx->stream));
+    const size_t tmp_bytes = std::max(ts_sort, std::max(ts_rle, ts_sel));
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_keys = 0, o_keys_s = o_keys + up(max_slice * 8), o_cnt = o_keys_s + up(max_slice * 8), o_keep = o_cnt + up(max_slice * 4),
+                 o_runs = o_keep + up(max_slice), o_tmp = o_runs + 256, pool_bytes = o_tmp + up(tmp_bytes);
+    rc_dev_tmp b_pool;
+    const double ta0 = now();
+    RC_CHECK_HIP(ctx, b_pool.alloc(pool_bytes));
+    T.alloc += now() - ta0;
+    char *pool = b_pool.as<char>();
+    uint64_t *keys = (uint64_t *)(pool + o_keys), *keys_s = (uint64_t *)(pool + o_keys_s);
+    uint32_t *cnt = (uint32_t *)(pool + o_cnt);
+    uint8_t *keep = (uint8_t *)(pool + o_keep);
+    size_t *d_runs = (size_t *)(pool + o_runs);
+    void *tmp = pool + o_tmp;
+    unsigned long long occ_total = 0;
+    for (uint32_t p = 0; p < P; ++p) occ_total += hist[p];
+    for (uint32_t p = 0; p < P; ++p) {
+        const size_t m = (size_t)hist[p];
+        if (m == 0) continue;
+        RC_CHECK_HIP(ctx, hipMemsetAsync(b_cursor.p, 0, 8, ctx->stream));
+        for (const auto &a : arenas) {
+            const unsigned G = (unsigned)((a.bytes + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
+            hipLaunchKernelGGL(k_count_scan<1>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, (const uint8_t *)a.p, a.bytes, k, P, p,
+                               (unsigned long long *)nullptr, keys, b_cursor.as<unsigned long long>());
+        }
+        RC_CHECK_HIP(ctx, hipGetLastError());
+        double tp = now();
+        if (timing) {
+            RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            T.emit += now() - tp;
+            tp = now();
+        }
+        size_t t1 = tmp_bytes;
+        RC_CHECK_HIP(ctx, rocprim::radix_sort_keys(tmp, t1, keys, keys_s, m, 0, 2 * k > 64 ? 64 : 2 * k, ctx->stream));
+        if (timing) {
+            RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            T.sort += now() - tp;
+            tp = now();
+        }
+        t1 = tmp_bytes;
+        RC_CHECK_HIP(ctx, rocprim::run_length_encode(tmp, t1, keys_s, (unsigned int)m, keys, cnt, d_runs, ctx->stream));
+        size_t runs = 0;
+        RC_CHECK_HIP(ctx, hipMemcpyAsync(&runs, d_runs, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
+        RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        T.rle += now() - tp;
+        if (runs == 0) continue;
+        const rc_count_pass pass = {p, P, hist, occ_total, keys, cnt, runs, keys_s, keep, d_runs, tmp, tmp_bytes};
+        const int rc = consume(pass);
+        if (rc) return rc;
+    }
+    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RC_OK;
+}
+
+int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers)
+{
+    if (!ctx->cnt_active) {
+        rc_set_error(ctx, "count_finish: call rc_table_count_begin first");
+        return RC_ERR_STATE;
+    }
+    ctx->cnt_active = false;
+    // RC_COUNT_TIMING=1 (dev): where finish() spends its time, on stderr
+    static const bool timing = getenv("RC_COUNT_TIMING") != nullptr;
+    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_begin = now();
+    rc_count_times T;
+    double t_sel = 0;  // (with the synchronisations the selection needs anyway)
+    struct release_on_exit {
+        rc_ctx *c;
+        ~release_on_exit() { rc_count_release(c); }  // (an error leaves nothing behind; success with cnt_keep has moved the arenas out)
+    } guard{ctx};
+    // rc_table_count_spectrum: every slice's run-length counts, before the min_count filter, into one device array
+    const uint32_t spec_bin = ctx->spec_arm;
+    rc_dev_tmp b_spec;
+    if (spec_bin) {
+        RC_CHECK_HIP(ctx, b_spec.alloc(((size_t)spec_bin + 5) * 8));
+        RC_CHECK_HIP(ctx, hipMemsetAsync(b_spec.p, 0, ((size_t)spec_bin + 5) * 8, ctx->stream));
+    }
     // The kept entries of all passes go straight into the two arrays the table is built from.  Their number is known only
     // at the end: the arrays are sized from the first pass that keeps anything (its share of the occurrences, + 15 %) and
-    // regrown in the rare case a later pass does not fit.  One allocation holds the passes' scratch.  (Round 3 allocated
-    // per pass and concatenated at the end: some forty hipMalloc / hipFree calls, each a round trip through the kernel
-    // driver -- 0.1 s on a quiet host, 0.5 s and more on a busy one, against 0.2 s for the counting itself.)
+    // regrown in the rare case a later pass does not fit.
     rc_dev_tmp b_allk, b_allc;
     size_t total_kept = 0, cap_kept = 0;
-    if (max_slice > 0) {
-        size_t ts_sort = 0, ts_rle = 0, ts_sel = 0;
-        RC_CHECK_HIP(ctx, rocprim::radix_sort_keys(nullptr, ts_sort, (uint64_t *)nullptr, (uint64_t *)nullptr, max_slice, 0, 2 * k > 64 ? 64 : 2 * k, ctx->stream));
-        RC_CHECK_HIP(ctx, rocprim::run_length_encode(nullptr, ts_rle, (uint64_t *)nullptr, (unsigned int)max_slice, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                                     (size_t *)nullptr, ctx->stream));
-        RC_CHECK_HIP(ctx, rocprim::select(nullptr, ts_sel, (uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t *)nullptr, (size_t *)nullptr, max_slice, ctx->stream));
-        const size_t tmp_bytes = std::max(ts_sort, std::max(ts_rle, ts_sel));
-        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t o_keys = 0, o_keys_s = o_keys + up(max_slice * 8), o_cnt = o_keys_s + up(max_slice * 8), o_keep = o_cnt + up(max_slice * 4),
-                     o_runs = o_keep + up(max_slice), o_tmp = o_runs + 256, pool_bytes = o_tmp + up(tmp_bytes);
-        rc_dev_tmp b_pool;
-        const double ta0 = now();
-        RC_CHECK_HIP(ctx, b_pool.alloc(pool_bytes));
-        t_alloc += now() - ta0;
-        char *pool = b_pool.as<char>();
-        uint64_t *keys = (uint64_t *)(pool + o_keys), *keys_s = (uint64_t *)(pool + o_keys_s);
-        uint32_t *cnt = (uint32_t *)(pool + o_cnt);
-        uint8_t *keep = (uint8_t *)(pool + o_keep);
-        size_t *d_runs = (size_t *)(pool + o_runs);
-        void *tmp = pool + o_tmp;
-        unsigned long long occ_total = 0;
-        for (uint32_t p = 0; p < P; ++p) occ_total += hist[p];
-        for (uint32_t p = 0; p < P; ++p) {
-            const size_t m = (size_t)hist[p];
-            if (m == 0) continue;
-            RC_CHECK_HIP(ctx, hipMemsetAsync(b_cursor.p, 0, 8, ctx->stream));
-            for (const auto &a : ctx->cnt_arenas) {
-                const unsigned G = (unsigned)((a.bytes + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
-                hipLaunchKernelGGL(k_count_scan<1>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, (const uint8_t *)a.p, a.bytes, k, P, p,
-                                   (unsigned long long *)nullptr, keys, b_cursor.as<unsigned long long>());
-            }
-            RC_CHECK_HIP(ctx, hipGetLastError());
-            double tp = now();
-            if (timing) {
-                RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                t_emit += now() - tp;
-                tp = now();
-            }
-            size_t t1 = tmp_bytes;
-            RC_CHECK_HIP(ctx, rocprim::radix_sort_keys(tmp, t1, keys, keys_s, m, 0, 2 * k > 64 ? 64 : 2 * k, ctx->stream));
-            if (timing) {
-                RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                t_sort += now() - tp;
-                tp = now();
-            }
-            t1 = tmp_bytes;
-            RC_CHECK_HIP(ctx, rocprim::run_length_encode(tmp, t1, keys_s, (unsigned int)m, keys, cnt, d_runs, ctx->stream));
-            size_t runs = 0;
-            RC_CHECK_HIP(ctx, hipMemcpyAsync(&runs, d_runs, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
-            RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            t_rle += now() - tp;
-            if (runs == 0) continue;
-            tp = now();
-            if (spec_bin) {
-                const int rs = rc_launch_spectrum_counts(ctx, ctx->stream, cnt, runs, spec_bin, b_spec.as<unsigned long long>());
-                if (rs) return rs;
-            }
-            hipLaunchKernelGGL(k_flag_keep, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, ctx->stream, keys, cnt, runs, min_count, keep);
-            // the kept keys land in keys_s (free again) and are copied out; their counts go through a second select into the
-            // same buffer and from there, clamped to int32, to their place
-            t1 = tmp_bytes;
-            RC_CHECK_HIP(ctx, rocprim::select(tmp, t1, keys, keep, keys_s, d_runs, runs, ctx->stream));
-            size_t nsel = 0;
-            RC_CHECK_HIP(ctx, hipMemcpyAsync(&nsel, d_runs, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
-            RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            t_sel += now() - tp;
-            if (nsel == 0) continue;
-            if (total_kept + nsel > cap_kept) {
-                const double ta1 = now();
-                // what this pass kept of its occurrences, applied to the occurrences still to come
-                unsigned long long seen = 0;
-                for (uint32_t q = 0; q <= p; ++q) seen += hist[q];
-                const double per_occ_kept = (double)(total_kept + nsel) / (double)(seen ? seen : 1);
-                size_t want = (size_t)(per_occ_kept * (double)occ_total * (cap_kept ? 1.5 : 1.15)) + ((size_t)1 << 20);
-                static const bool tight = getenv("RC_COUNT_TIGHT") != nullptr;  // tests: no slack, every pass regrows the arrays
-                if (want < total_kept + nsel || tight) want = total_kept + nsel;
-                rc_dev_tmp nk, nc;
-                RC_CHECK_HIP(ctx, nk.alloc((want + 1) * 8));
-                RC_CHECK_HIP(ctx, nc.alloc((want + 1) * 4));
-                if (total_kept) {
-                    RC_CHECK_HIP(ctx, hipMemcpyAsync(nk.p, b_allk.p, total_kept * 8, hipMemcpyDeviceToDevice, ctx->stream));
-                    RC_CHECK_HIP(ctx, hipMemcpyAsync(nc.p, b_allc.p, total_kept * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                }
-                std::swap(nk.p, b_allk.p);
-                std::swap(nc.p, b_allc.p);
-                cap_kept = want;
-                t_alloc += now() - ta1;
-            }
-            RC_CHECK_HIP(ctx, hipMemcpyAsync(b_allk.as<uint64_t>() + total_kept, keys_s, nsel * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            uint32_t *selc = reinterpret_cast<uint32_t *>(keys_s);  // (keys_s was copied out: the stream orders the reuse)
-            t1 = tmp_bytes;
-            RC_CHECK_HIP(ctx, rocprim::select(tmp, t1, cnt, keep, selc, d_runs, runs, ctx->stream));
-            hipLaunchKernelGGL(k_u32_to_i32_clamped, dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, ctx->stream, selc, b_allc.as<int32_t>() + total_kept, nsel);
-            RC_CHECK_HIP(ctx, hipGetLastError());
-            total_kept += nsel;
+    const int prc = rc_count_passes(ctx, ctx->cnt_arenas, ctx->cnt_total, timing, T, [&](const rc_count_pass &s) -> int {
+        const size_t runs = s.runs;
+        const double tp = now();
+        if (spec_bin) {
+            const int rs = rc_launch_spectrum_counts(ctx, ctx->stream, s.cnt, runs, spec_bin, b_spec.as<unsigned long long>());
+            if (rs) return rs;
         }
+        hipLaunchKernelGGL(k_flag_keep, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, ctx->stream, s.uniq, s.cnt, runs, min_count, s.keep);
+        // the kept keys land in keys_s (free again) and are copied out; their counts go through a second select into the
+        // same buffer and from there, clamped to int32, to their place
+        size_t t1 = s.tmp_bytes;
+        RC_CHECK_HIP(ctx, rocprim::select(s.tmp, t1, s.uniq, s.keep, s.keys_s, s.d_runs, runs, ctx->stream));
+        size_t nsel = 0;
+        RC_CHECK_HIP(ctx, hipMemcpyAsync(&nsel, s.d_runs, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
         RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
+        t_sel += now() - tp;
+        if (nsel == 0) return RC_OK;
+        if (total_kept + nsel > cap_kept) {
+            const double ta1 = now();
+            // what this pass kept of its occurrences, applied to the occurrences still to come
+            unsigned long long seen = 0;
+            for (uint32_t q = 0; q <= s.p; ++q) seen += s.hist[q];
+            const double per_occ_kept = (double)(total_kept + nsel) / (double)(seen ? seen : 1);
+            size_t want = (size_t)(per_occ_kept * (double)s.occ_total * (cap_kept ? 1.5 : 1.15)) + ((size_t)1 << 20);
+            static const bool tight = getenv("RC_COUNT_TIGHT") != nullptr;  // tests: no slack, every pass regrows the arrays
+            if (want < total_kept + nsel || tight) want = total_kept + nsel;
+            rc_dev_tmp nk, nc;
+            RC_CHECK_HIP(ctx, nk.alloc((want + 1) * 8));
+            RC_CHECK_HIP(ctx, nc.alloc((want + 1) * 4));
+            if (total_kept) {
+                RC_CHECK_HIP(ctx, hipMemcpyAsync(nk.p, b_allk.p, total_kept * 8, hipMemcpyDeviceToDevice, ctx->stream));
+                RC_CHECK_HIP(ctx, hipMemcpyAsync(nc.p, b_allc.p, total_kept * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            }
+            std::swap(nk.p, b_allk.p);
+            std::swap(nc.p, b_allc.p);
+            cap_kept = want;
+            T.alloc += now() - ta1;
+        }
+        RC_CHECK_HIP(ctx, hipMemcpyAsync(b_allk.as<uint64_t>() + total_kept, s.keys_s, nsel * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        uint32_t *selc = reinterpret_cast<uint32_t *>(s.keys_s);  // (keys_s was copied out: the stream orders the reuse)
+        t1 = s.tmp_bytes;
+        RC_CHECK_HIP(ctx, rocprim::select(s.tmp, t1, s.cnt, s.keep, selc, s.d_runs, runs, ctx->stream));
+        hipLaunchKernelGGL(k_u32_to_i32_clamped, dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, ctx->stream, selc, b_allc.as<int32_t>() + total_kept, nsel);
+        RC_CHECK_HIP(ctx, hipGetLastError());
+        total_kept += nsel;
+        return RC_OK;
+    });
+    if (prc) return prc;
     if (spec_bin) {
         std::vector<uint64_t> f((size_t)spec_bin + 5);
         RC_CHECK_HIP(ctx, hipMemcpyAsync(f.data(), b_spec.p, f.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1682,7 +1742,7 @@ int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers)
     int rc = rc_build_table_from_device_pairs(ctx, b_allk.as<uint64_t>(), b_allc.as<int32_t>(), total_kept);
     if (timing)
         fprintf(stderr, "[rc count timing] finish %.3f s: histogram + %u passes %.3f (emit %.3f, sort %.3f, run lengths %.3f, select %.3f, hipMalloc %.3f), reads released %.3f, table build %.3f\n",
-                now() - t_begin, P, t_passes - t_begin, t_emit, t_sort, t_rle, t_sel, t_alloc, t_concat - t_passes, now() - t_concat);
+                now() - t_begin, T.P, t_passes - t_begin, T.emit, T.sort, T.rle, t_sel, T.alloc, t_concat - t_passes, now() - t_concat);
     if (rc != RC_OK) rc_kept_release(ctx);
     if (rc == RC_OK && total_kept) {  // (rc_estimate_error_rate takes them from here; rc_table_release frees them)
         ctx->counted_codes = b_allk.p;
@@ -1691,6 +1751,149 @@ int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers)
     }
     if (n_kmers) *n_kmers = (int64_t)total_kept;
     return rc;
+}
+
+// ---- recount session (include/rcorrector_amd.h: rc_recount_begin): a second, read-only use of the counter ------------------
+// The session's arenas live in chunks of their own (rec_chunks), so neither the counter's session nor the kept arenas are
+// touched; finish() runs the shared pass loop over them and hands every slice to the census kernel instead of the table build.
+#define RC_CENSUS_UNROLL 2
+
+// Per lane one distinct canonical code of a sorted slice and its count: is the code in the table (GetCount != 0), and the
+// count into the spectrum (rc_spec_add, as k_spectrum_counts).  The codes are sorted by value, the table is addressed by
+// hash, so every probe is a scattered 64-byte bucket read.  What round 6 learnt about such reads (docs/rounds/r6.md,
+// tools/microbench_bucket.hip): their cost is the number of load INSTRUCTIONS times the lines each touches, not the bytes
+// -- so the probe is rc_table_lookup_quad (a quad reads a bucket together: four instructions of 16 lines for four buckets
+// instead of four of 64), and a lane keeps RC_CENSUS_UNROLL codes, eight such loads, in flight: with 16 waves a CU that is
+// 128 outstanding instructions, where the microbenchmark's rate out of a table beyond the L2 no longer rose.
+// out = freq[max_bin + 1], {distinct, total, unique, max_count}, {absent_distinct, absent_total}
+__global__ __launch_bounds__(RC_SPEC_THREADS) void k_census(rc_table_view T, const uint64_t *__restrict__ uniq, const uint32_t *__restrict__ cnt, size_t n,
+                                                            uint32_t max_bin, uint32_t lds_bins, unsigned long long *__restrict__ out)
+{
+    __shared__ uint32_t s_small[RC_SPEC_WAVES * RC_SPEC_SMALL];
+    extern __shared__ uint32_t s_big[];
+    rc_spec_zero(s_small, s_big, lds_bins);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t *s_wave = s_small + w * RC_SPEC_SMALL;
+    rc_spec_acc A;
+    unsigned long long absent_distinct = 0;  // wave-uniform (ballot counts)
+    unsigned long long absent_total = 0;     // per lane
+    const size_t per_wave = 64 * RC_CENSUS_UNROLL, stride = (size_t)gridDim.x * RC_SPEC_WAVES * per_wave;
+    for (size_t base = ((size_t)blockIdx.x * RC_SPEC_WAVES + w) * per_wave; base < n; base += stride) {  // (wave-uniform: the quad lookup wants every lane)
+        uint64_t key[RC_CENSUS_UNROLL];
+        uint32_t c[RC_CENSUS_UNROLL];
+        int in_table[RC_CENSUS_UNROLL];
+#pragma unroll
+        for (int u = 0; u < RC_CENSUS_UNROLL; ++u) {
+            const size_t i = base + (size_t)u * 64 + lane;
+            key[u] = i < n ? uniq[i] : 0;
+            c[u] = i < n ? cnt[i] : 0;  // (a run length is at least 1: 0 = no code for this lane)
+        }
+#pragma unroll
+        for (int u = 0; u < RC_CENSUS_UNROLL; ++u) in_table[u] = rc_table_lookup_quad<true>(T, key[u], c[u] != 0);
+#pragma unroll
+        for (int u = 0; u < RC_CENSUS_UNROLL; ++u) {
+            const bool valid = c[u] != 0, absent = valid && in_table[u] == 0;
+            rc_spec_add(A, valid, c[u], max_bin, lds_bins, s_wave, s_big, out);
+            absent_distinct += (unsigned long long)__popcll(__ballot(absent));
+            if (absent) absent_total += c[u];
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) absent_total += __shfl_xor(absent_total, o, 64);
+    if (lane == 0 && absent_distinct) {  // one atomic per wavefront and quantity
+        atomicAdd(&out[(size_t)max_bin + 5], absent_distinct);
+        atomicAdd(&out[(size_t)max_bin + 6], absent_total);
+    }
+    rc_spec_flush(A, max_bin, lds_bins, s_small, s_big, out);
+}
+
+// d_out: max_bin + 1 + 6 uint64, zeroed by the caller before the first launch; adds one slice (stream st)
+static int rc_launch_census(rc_ctx *ctx, hipStream_t st, const uint64_t *d_uniq, const uint32_t *d_cnt, size_t n, uint32_t max_bin, unsigned long long *d_out)
+{
+    if (n == 0) return RC_OK;
+    const uint32_t lds = rc_spec_lds_bins(max_bin);
+    const size_t bytes = rc_spec_lds_bytes(lds);
+    RC_CHECK_HIP(ctx, rc_spec_allow_lds(reinterpret_cast<const void *>(k_census), bytes));
+    const size_t per_block = (size_t)RC_SPEC_WAVES * 64 * RC_CENSUS_UNROLL;
+    const unsigned G = (unsigned)std::min<size_t>(RC_SPEC_MAX_BLOCKS, (n + per_block - 1) / per_block);
+    hipLaunchKernelGGL(k_census, dim3(G), dim3(RC_SPEC_THREADS), bytes, st, rc_view(ctx), d_uniq, d_cnt, n, max_bin, lds, d_out);
+    RC_CHECK_HIP(ctx, hipGetLastError());
+    return RC_OK;
+}
+
+void rc_recount_release(rc_ctx *ctx)
+{
+    for (auto &a : ctx->rec_chunks)
+        if (a.p) (void)hipFree(a.p);
+    ctx->rec_chunks.clear();
+    ctx->rec_arenas.clear();
+    ctx->rec_chunk_used = 0;
+    ctx->rec_total = 0;
+    ctx->rec_active = false;
+}
+
+int rc_recount_begin_session(rc_ctx *ctx, uint32_t max_bin)
+{
+    rc_recount_release(ctx);  // (a session that was never finished)
+    ctx->rec_bin = max_bin;
+    ctx->rec_active = true;
+    return RC_OK;
+}
+
+// a copy of the arena into the session's chunks, on stream `st` of the session's device (a slot lane's for the batches it ran)
+int rc_recount_append(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_device, hipStream_t st)
+{
+    if (nbytes == 0) return RC_OK;
+    if (nbytes >= (1ull << 32)) {
+        rc_set_error(ctx, "recount: an arena must be below 2^32 bytes (add it in pieces)");
+        return RC_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lock(ctx->rec_mutex);  // (batches of several slots may complete on threads of their own)
+    const size_t cap = rc_count_retain_cap();
+    int rc = RC_OK;
+    if (ctx->rec_total + nbytes > cap) {
+        rc_set_error(ctx, "recount: %zu MB of reads exceed what a counting session keeps in HBM (%zu MB, RC_COUNT_RETAIN_MB)", (ctx->rec_total + nbytes) >> 20, cap >> 20);
+        rc = RC_ERR_NOMEM;
+    } else {
+        rc = rc_arena_keep(ctx, ctx->rec_arenas, ctx->rec_chunks, ctx->rec_chunk_used, ctx->rec_total, seq, nbytes, from_device, st, "recount_add");
+    }
+    if (rc) rc_recount_release(ctx);  // an error ends the session and leaves nothing allocated
+    return rc;
+}
+
+// out: freq[rec_bin + 1], then distinct, total, unique, max_count, absent_distinct, absent_total
+int rc_recount_finish_session(rc_ctx *ctx, std::vector<uint64_t> *out)
+{
+    static const bool timing = getenv("RC_COUNT_TIMING") != nullptr;
+    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_begin = now();
+    struct release_on_exit {
+        rc_ctx *c;
+        ~release_on_exit() { rc_recount_release(c); }  // (success or error: the session is over, nothing stays allocated)
+    } guard{ctx};
+    const uint32_t max_bin = ctx->rec_bin;
+    const size_t words = (size_t)max_bin + 7;
+    rc_dev_tmp b_out;
+    RC_CHECK_HIP(ctx, b_out.alloc(words * 8));
+    RC_CHECK_HIP(ctx, hipMemsetAsync(b_out.p, 0, words * 8, ctx->stream));
+    rc_count_times T;
+    double t_census = 0;
+    const int prc = rc_count_passes(ctx, ctx->rec_arenas, ctx->rec_total, timing, T, [&](const rc_count_pass &s) -> int {
+        const double tp = now();
+        const int rc = rc_launch_census(ctx, ctx->stream, s.uniq, s.cnt, s.runs, max_bin, b_out.as<unsigned long long>());
+        if (rc == RC_OK && timing) {
+            RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            t_census += now() - tp;
+        }
+        return rc;
+    });
+    if (prc) return prc;
+    out->assign(words, 0);
+    RC_CHECK_HIP(ctx, hipMemcpyAsync(out->data(), b_out.p, words * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (timing)
+        fprintf(stderr, "[rc recount timing] finish %.3f s: histogram + %u passes over %zu MB (emit %.3f, sort %.3f, run lengths %.3f, census %.3f, hipMalloc %.3f)\n",
+                now() - t_begin, T.P, ctx->rec_total >> 20, T.emit, T.sort, T.rle, t_census, T.alloc);
+    return RC_OK;
 }
 
 // n bytes from device memory of one GPU to device memory of another (or the same), queued on `st`, a stream of the destination's
