@@ -188,6 +188,48 @@ int rc_recount_follow(rc_ctx *ctx, int on);
 /* freq[max_bin + 1] (begin's max_bin); stats may be NULL.  No reference counterpart. */
 int rc_recount_finish(rc_ctx *ctx, uint64_t *freq, rc_recount_stats *stats);
 
+/* ---- correction report: what was changed, where in the read, and in which reads ---------------------------------------------
+ * While the report is armed on a context, every batch that completes on it -- rc_correct_batch, rc_correct_batch_traced,
+ * rc_wait, rc_wait_packed, rc_wait_resident (the batches of slots that run in lanes included), rc_correct_device (in stream
+ * order, at the end of the call) and rc_correct_read -- is compared on the GPU with a copy of its arena taken before the
+ * first correction kernel, and every byte that differs (a correction only ever writes one of ACGT over a different byte,
+ * ErrorCorrection.cpp:1468-1479) is counted below; each batch once: a packed or resident batch that came back with
+ * RC_STATUS_NOSPACE is counted when its resubmission completes.  Not armed, those calls launch, copy and allocate nothing
+ * for it; armed or not, the corrected reads, ret / l / m / h, rc_summary and rc_table_digest are the same.
+ *   mate 0: every read of mode 0, the first half of a mode-1 arena, the even reads of mode 2; mate 1: the others.
+ *   Positions are 0-based; a position (or length) of RC_REPORT_MAX_LEN - 1 or more is counted in the last entry (the
+ *   reference's reads have at most 1023 bases, utils.h:7).
+ *   subst[from][to]: from = 0..3 for the letters A C G T exactly as the kernels read them -- upper case only: a lower-case
+ *   letter is to them a letter outside ACGT, and is counted like N and everything else in row 4 --, to = A C G T.
+ *   by_qual: [0] the changed base was of low quality by the very test the correction applies (quality byte <=
+ *   badQualityThreshold, or its quality bit clear), [1] of high quality, [2] the read came without qualities (its first
+ *   quality byte is 0: FASTA, Reads.h:241).
+ *   per_read[c]: reads with c changed bases, c = 0 included; the last entry: RC_REPORT_MAX_PER_READ or more.
+ * begin: RC_STATUS_STATE if armed already (needs no table).  get: waits for the report kernels outstanding on the context and
+ * its lanes, then copies the counts out; the report stays armed and goes on accumulating; RC_STATUS_STATE if not armed.
+ * end: disarms and frees (rc_destroy does too); RC_STATUS_STATE if not armed; a packed / resident batch in flight across end is
+ * in no report.  A byte batch (rc_submit) is counted once its kernels are queued, whether or not the caller waits for it.
+ * Armed, the comparison reads the arena in aligned 16-byte pieces: rc_correct_device's d_seq is read (never written) up to
+ * 15 bytes in front of its first and behind its last byte, within the 16-byte granules those bytes lie in.
+ * No reference counterpart. */
+#define RC_REPORT_MAX_LEN 1024
+#define RC_REPORT_MAX_PER_READ 64
+typedef struct {
+    uint64_t reads[2];           /* reads seen */
+    uint64_t reads_changed[2];   /* ... with at least one changed base */
+    uint64_t reads_unfixable[2]; /* ... with ret == -1 */
+    uint64_t changes[2];         /* changed bases */
+    uint64_t len_hist[2][RC_REPORT_MAX_LEN]; /* reads by length (reads covering position p = the sum of the entries above p) */
+    uint64_t by_pos5[2][RC_REPORT_MAX_LEN];  /* changes by distance from the read's first base */
+    uint64_t by_pos3[2][RC_REPORT_MAX_LEN];  /* changes by distance from its last base (0 = the last base) */
+    uint64_t subst[5][4];        /* changes by original letter (A C G T, other) and new letter (A C G T) */
+    uint64_t by_qual[3];         /* changes on a low-quality base, on a high-quality base, in reads without qualities */
+    uint64_t per_read[RC_REPORT_MAX_PER_READ + 1]; /* reads by number of changed bases */
+} rc_change_report;
+int rc_change_report_begin(rc_ctx *ctx);
+int rc_change_report_get(rc_ctx *ctx, rc_change_report *out);
+int rc_change_report_end(rc_ctx *ctx);
+
 /* ---- run parameters (globals of main.cpp:17-30) ----------------------------------------------- */
 /* replaces main.cpp:310-358 (ERROR_RATE estimation).  Uses the entries parsed by the last
  * rc_table_load_jfdump() in file order -- or, for a table that was counted here or built from

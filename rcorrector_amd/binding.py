@@ -17,6 +17,7 @@ ABI_SYMBOLS = [
     "rc_table_count_reads_device", "rc_table_write_jfdump", "rc_table_share", "rc_table_replicate", "rc_table_replicate_async", "rc_table_lookup", "rc_table_export", "rc_table_digest", "rc_table_layout", "rc_table_stats",
     "rc_table_count_spectrum", "rc_table_spectrum",
     "rc_recount_begin", "rc_recount_add", "rc_recount_add_device", "rc_recount_follow", "rc_recount_finish",
+    "rc_change_report_begin", "rc_change_report_get", "rc_change_report_end",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
@@ -74,6 +75,16 @@ class _SpectrumStats(C.Structure):
 
 class _RecountStats(C.Structure):
     _fields_ = [("all", _SpectrumStats), ("absent_distinct", C.c_uint64), ("absent_total", C.c_uint64)]
+
+
+REPORT_MAX_LEN = 1024       # RC_REPORT_MAX_LEN
+REPORT_MAX_PER_READ = 64    # RC_REPORT_MAX_PER_READ
+
+
+class _ChangeReport(C.Structure):
+    _fields_ = [("reads", C.c_uint64 * 2), ("reads_changed", C.c_uint64 * 2), ("reads_unfixable", C.c_uint64 * 2), ("changes", C.c_uint64 * 2),
+                ("len_hist", C.c_uint64 * REPORT_MAX_LEN * 2), ("by_pos5", C.c_uint64 * REPORT_MAX_LEN * 2), ("by_pos3", C.c_uint64 * REPORT_MAX_LEN * 2),
+                ("subst", C.c_uint64 * 4 * 5), ("by_qual", C.c_uint64 * 3), ("per_read", C.c_uint64 * (REPORT_MAX_PER_READ + 1))]
 
 
 class _DeviceBatch(C.Structure):
@@ -148,6 +159,9 @@ def load_library():
     L.rc_recount_add_device.argtypes = [vp, vp, C.c_size_t]
     L.rc_recount_follow.argtypes = [vp, C.c_int]
     L.rc_recount_finish.argtypes = [vp, vp, C.POINTER(_RecountStats)]
+    L.rc_change_report_begin.argtypes = [vp]
+    L.rc_change_report_get.argtypes = [vp, C.POINTER(_ChangeReport)]
+    L.rc_change_report_end.argtypes = [vp]
     L.rc_estimate_error_rate.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.rc_bad_quality_from_hist.restype = C.c_char
     L.rc_bad_quality_from_hist.argtypes = [vp, vp, C.c_int32]
@@ -394,6 +408,24 @@ class Context:
         a = st.all
         return freq, {"distinct": a.distinct, "total": a.total, "unique": a.unique, "max_count": a.max_count,
                       "absent_distinct": st.absent_distinct, "absent_total": st.absent_total}
+
+    # ---- correction report: what was changed, where in the read, and in which reads ----
+    def change_report_begin(self):
+        """rc_change_report_begin: from now on every batch that completes on this context (any entry point, slot lanes
+        included) is compared on the GPU with its uncorrected arena and counted, each batch once."""
+        self._ck(self._L.rc_change_report_begin(self._h))
+
+    def change_report(self):
+        """rc_change_report_get: dict of uint64 arrays named and shaped as the fields of rc_change_report -- reads,
+        reads_changed, reads_unfixable, changes [2 mates]; len_hist, by_pos5, by_pos3 [2][1024]; subst [5 from: A C G T other]
+        [4 to: A C G T]; by_qual [low, high, none]; per_read [65].  The report stays armed and cumulative."""
+        r = _ChangeReport()
+        self._ck(self._L.rc_change_report_get(self._h, C.byref(r)))
+        return {name: np.ctypeslib.as_array(getattr(r, name)).astype(np.uint64) for name, _ in _ChangeReport._fields_}
+
+    def change_report_end(self):
+        """rc_change_report_end: disarms the report and frees what it held."""
+        self._ck(self._L.rc_change_report_end(self._h))
 
     # ---- run parameters ----
     def estimate_error_rate(self, wk=0.95):

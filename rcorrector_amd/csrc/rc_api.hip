@@ -249,7 +249,7 @@ void rc_destroy(rc_ctx *c)
             rc_hbuf *hb[] = {&sl.p_seq, &sl.p_qual, &sl.p_off, &sl.p_res, &sl.p_in, &sl.p_fix, &sl.p_nfix};
             for (rc_hbuf *h : hb)
                 if (h->p) (void)hipHostFree(h->p);
-            rc_dbuf *db[] = {&sl.d_seq, &sl.d_qual, &sl.d_off, &sl.d_res, &sl.d_packed, &sl.d_exc, &sl.d_fix};
+            rc_dbuf *db[] = {&sl.d_seq, &sl.d_qual, &sl.d_off, &sl.d_res, &sl.d_packed, &sl.d_exc, &sl.d_fix, &sl.d_rep};
             for (rc_dbuf *d : db)
                 if (d->p) (void)hipFree(d->p);
             hipEvent_t ev[] = {sl.e_h2d, sl.e_k, sl.e_done};
@@ -264,6 +264,7 @@ void rc_destroy(rc_ctx *c)
         if (a.p) (void)hipFree(a.p);
     rc_kept_release(ctx);
     rc_recount_release(ctx);
+    rc_report_release(ctx);
     rc_table_release(ctx);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

@@ -13,7 +13,12 @@ int rc_probe_device(rc_ctx *ctx, const uint8_t *d_seq, uint64_t nbytes, int32_t 
 }
 
 
-int rc_correct_device(rc_ctx *ctx, const rc_device_batch *b) { return rc_correct_device_impl(ctx, b, 0xFFFFFFFFu, 0); }
+// (the correction report: rc_correct_device has no wait -- the batch counts at the end of the call, in stream order)
+int rc_correct_device(rc_ctx *ctx, const rc_device_batch *b)
+{
+    const int rc = rc_correct_device_impl(ctx, b, 0xFFFFFFFFu, 0);
+    return rc ? rc : rc_report_count(ctx, b, 0xFFFFFFFFu, 0, -1, nullptr, nullptr);
+}
 
 // qual_split / qual_base2 (quality-bit mode only): arena bytes from qual_split on have their bits at
 // byte qual_base2 of d_qual -- the second arena of a paired host batch, whose bit array is separate
@@ -42,6 +47,8 @@ int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_
     }
     RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     int rc;
+    // the correction report, if one is armed: the arena as it is now (the entry point counts the batch against it, once)
+    if ((rc = rc_report_snapshot(ctx, b->d_seq, (size_t)b->nbytes))) return rc;
     bool fused = false;  // probe and threshold kernels ran as one
     if ((rc = rc_dbuf_reserve(ctx, &ctx->counts, (size_t)b->nbytes * 4 + 256))) return rc;
     if ((rc = rc_dbuf_reserve(ctx, &ctx->strong, (size_t)b->n_reads * 4 + 256))) return rc;
@@ -266,6 +273,7 @@ int rc_correct_read(rc_ctx *ctx, char *seq, const char *qual, int32_t pair_stron
     int rc = one_read_upload(ctx, seq, qual, a, &n1);
     if (rc) return rc;
     a.pair_override = pair_strong_threshold;
+    if ((rc = rc_report_snapshot(ctx, a.seq, n1))) return rc;
     if ((rc = rc_launch_probe(ctx, a.seq, n1, (int32_t *)ctx->counts.p))) return rc;
     // no threshold kernel, no classification: k_correct computes the read's own threshold (its single-end front end) and
     // takes the pair's from the argument, exactly the reference's call
@@ -274,6 +282,16 @@ int rc_correct_read(rc_ctx *ctx, char *seq, const char *qual, int32_t pair_stron
     ctx->cand_ready = false;
     if ((rc = rc_launch_correct(ctx, a))) return rc;
     if ((rc = rc_launch_summary(ctx, a.ret, 1))) return rc;
+    {
+        rc_device_batch db = rc_device_batch();
+        db.n_reads = 1;
+        db.nbytes = n1;
+        db.d_seq = a.seq;
+        db.d_qual = a.qual;
+        db.d_off = a.off;
+        db.d_ret = a.ret;
+        if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, 0, nullptr, nullptr))) return rc;
+    }
     RC_CHECK_HIP(ctx, hipMemcpyAsync(seq, a.seq, n1 - 1, hipMemcpyDeviceToHost, ctx->stream));
     RC_CHECK_HIP(ctx, hipMemcpyAsync(ret, a.ret, 4, hipMemcpyDeviceToHost, ctx->stream));
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -629,7 +647,10 @@ int rc_submit(rc_ctx *c, const rc_batch *b, int slot)
     db.d_l = d_res + total;
     db.d_m = d_res + 2 * total;
     db.d_h = d_res + 3 * total;
-    if ((rc = rc_correct_device_impl(ctx, &db, qbits && b->mode == 1 ? (uint32_t)sl.bytes1 : 0xFFFFFFFFu, (uint32_t)qbase2))) return rc;
+    const uint32_t qsplit = qbits && b->mode == 1 ? (uint32_t)sl.bytes1 : 0xFFFFFFFFu;
+    if ((rc = rc_correct_device_impl(ctx, &db, qsplit, (uint32_t)qbase2))) return rc;
+    // (the correction report: no second submission on this path -- counted here, before the event rc_wait waits for)
+    if ((rc = rc_report_count(ctx, &db, qsplit, (uint32_t)qbase2, -1, nullptr, nullptr))) return rc;
     RC_CHECK_HIP(ctx, hipEventRecord(sl.e_k, ctx->stream));
     // results
     RC_CHECK_HIP(ctx, hipStreamWaitEvent(ctx->s_d2h, sl.e_k, 0));

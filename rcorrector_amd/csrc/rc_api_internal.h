@@ -52,6 +52,10 @@ struct rc_slot {
     rc_packed_batch *pb = nullptr;
     rc_resident_batch *rb = nullptr;  // rc_submit_resident: same slot state, the arena copied from the counter's kept arenas
     rc_dbuf d_packed, d_exc, d_fix;
+    // correction report: a packed / resident batch's counts wait here until its wait accepts it (a batch that did not fit its
+    // fix list comes again, and only then counts); rep_staged: this batch left some
+    rc_dbuf d_rep;
+    bool rep_staged = false;
     rc_hbuf p_in, p_fix, p_nfix;
     uint32_t fix_room = 0;
     bool fix_pinned = false;
@@ -75,4 +79,13 @@ void rc_lane_error(rc_ctx *ctx, const rc_ctx *lane);
 // rc_recount_follow: a batch has completed in ctx (a context or one of its slot lanes) and its corrected arena lies in d_seq --
 // appended to the open session of the context the batch was submitted to, on ctx's own stream; nothing without a session
 int rc_recount_take(rc_ctx *ctx, const void *d_seq, size_t nbytes);
+// rc_api_report.hip -- the correction report.  ctx is the context the batch runs in (a context or one of its slot lanes); the
+// report is that of the context the batch was submitted to.  All three do nothing while no report is armed.
+// snapshot: before the first correction kernel, on ctx's stream (rc_correct_device_impl does it for the batch entry points).
+// count: behind the last correction kernel -- the batch launched last on ctx against its snapshot, straight into the report
+// (staged == nullptr) or into `staged` (zeroed first), *did = something was launched.  commit: a staged batch into the report.
+int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes);
+int rc_report_count(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits, rc_dbuf *staged, bool *did);
+int rc_report_commit(rc_ctx *ctx, const rc_dbuf *staged);
+void rc_report_release(rc_ctx *ctx);
 }

@@ -201,6 +201,8 @@ int rc_submit_packed(rc_ctx *c, rc_packed_batch *b, int slot)
     db.d_m = d_res + 2 * total;
     db.d_h = d_res + 3 * total;
     if ((rc = rc_correct_device_impl(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0))) return rc;
+    // (the correction report: staged, the wait decides whether this submission is the one that counts)
+    if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0, &sl.d_rep, &sl.rep_staged))) return rc;
     // The fix list is written by the kernel straight into page-locked host memory (the caller's arrays, or the slot's
     // staging where those are pageable): a few bytes per read, consecutive entries from consecutive lanes.  A copy after
     // the kernels would have to wait for the count first -- a second round trip per batch on a stream of its own, which
@@ -265,6 +267,10 @@ int rc_wait_packed(rc_ctx *c, int slot)
     }
     // rc_recount_follow: before the slot can be reused (a batch that did not fit its fix list comes again and is taken then)
     if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;
+    if (sl.rep_staged) {  // the correction report: this submission is the one that counts
+        sl.rep_staged = false;
+        if (const int frc = rc_report_commit(ctx, &sl.d_rep)) return frc;
+    }
     const uint32_t *o_pos = (const uint32_t *)sl.p_fix.p;
     const uint8_t *o_chr = (const uint8_t *)sl.p_fix.p + (size_t)cap * 4;
     if (!sl.res_pinned) {
@@ -414,6 +420,8 @@ int rc_submit_resident(rc_ctx *c, rc_resident_batch *b, int slot)
     db.d_m = d_res + 2 * total;
     db.d_h = d_res + 3 * total;
     if ((rc = rc_correct_device_impl(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0))) return rc;
+    // (the correction report: staged, the wait decides whether this submission is the one that counts)
+    if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0, &sl.d_rep, &sl.rep_staged))) return rc;
     void *dp = nullptr, *dc = nullptr;  // (the fix list goes straight into page-locked host memory, as in rc_submit_packed)
     if (cap) {
         RC_CHECK_HIP(ctx, hipHostGetDevicePointer(&dp, sl.fix_pinned ? (void *)b->fix_pos : sl.p_fix.p, 0));
@@ -471,6 +479,10 @@ int rc_wait_resident(rc_ctx *c, int slot)
     }
     // rc_recount_follow: before the slot can be reused (a batch that did not fit its fix list comes again and is taken then)
     if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;
+    if (sl.rep_staged) {  // the correction report: this submission is the one that counts
+        sl.rep_staged = false;
+        if (const int frc = rc_report_commit(ctx, &sl.d_rep)) return frc;
+    }
     if (!sl.res_pinned) {
         const int32_t *r = (const int32_t *)sl.p_res.p;
         memcpy(b->ret, r, total * 4);

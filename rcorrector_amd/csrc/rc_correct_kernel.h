@@ -533,20 +533,7 @@ __device__ __forceinline__ void rc_load_read(W &w, const rc_kernel_args &A, rc_r
     for (int i = lane; i < len; i += 64) {
         S.base[i] = (unsigned char)rc_base_code(A.seq[o + i]);
         S.counts[i] = i < S.kcnt ? A.counts[o + i] : 0;
-        if (with_qual) {
-            if (A.qual_bits) {
-                // the vetoes only compare a quality with badQualityThreshold (ErrorCorrection.cpp:1313-1466) and
-                // test qual[0] != 0 (FASTQ marker): a bit per base stands in for the byte
-                uint32_t p = o + (uint32_t)i;
-                const uint8_t *qb = A.qual;
-                if (p >= A.qual_split) {
-                    p -= A.qual_split;
-                    qb += A.qual_base2;
-                }
-                S.qual[i] = ((qb[p >> 3] >> (p & 7u)) & 1u) ? (signed char)127 : (signed char)-128;
-            } else
-                S.qual[i] = (signed char)A.qual[o + i];
-        }
+        if (with_qual) S.qual[i] = rc_qual_at(A.qual, A.qual_bits, A.qual_split, A.qual_base2, o + (uint32_t)i);
     }
     w.sync();
     rc_build_masks(w, S);

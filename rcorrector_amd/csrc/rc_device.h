@@ -435,3 +435,20 @@ __device__ __forceinline__ void rc_spec_flush(rc_spec_acc &A, uint32_t max_bin, 
         if (v) atomicAdd(&out[b], (unsigned long long)v);
     }
 }
+
+// the quality of arena byte p as the correction sees it (and as the change report classes it: low = at most
+// badQualityThreshold): the byte, or in bit mode 127 / -128 for a set / clear bit
+__device__ __forceinline__ signed char rc_qual_at(const uint8_t *qual, int qual_bits, uint32_t qual_split, uint32_t qual_base2, uint32_t p)
+{
+    if (qual_bits) {
+        // the vetoes only compare a quality with badQualityThreshold (ErrorCorrection.cpp:1313-1466) and
+        // test qual[0] != 0 (FASTQ marker): a bit per base stands in for the byte
+        const uint8_t *qb = qual;
+        if (p >= qual_split) {
+            p -= qual_split;
+            qb += qual_base2;
+        }
+        return ((qb[p >> 3] >> (p & 7u)) & 1u) ? (signed char)127 : (signed char)-128;
+    }
+    return (signed char)qual[p];
+}

@@ -155,6 +155,41 @@ bool write_histo(const char *path, const std::vector<uint64_t> &freq)
     return fclose(fp) == 0 && ok;
 }
 
+bool write_change_report(const char *path, const rc_change_report &R, bool two_mates)
+{
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return false;
+    typedef unsigned long long ull;
+    const int mates = two_mates ? 2 : 1;
+    bool ok = true;
+    for (int m = 0; m < mates && ok; ++m)
+        ok = fprintf(fp, "reads\t%d\t%llu\t%llu\t%llu\n", m + 1, (ull)R.reads[m], (ull)R.reads_changed[m], (ull)R.reads_unfixable[m]) > 0;
+    for (int m = 0; m < mates && ok; ++m) ok = fprintf(fp, "changes\t%d\t%llu\n", m + 1, (ull)R.changes[m]) > 0;
+    int longest[2] = {0, 0};
+    for (int m = 0; m < mates; ++m)
+        for (int l = 0; l < RC_REPORT_MAX_LEN; ++l)
+            if (R.len_hist[m][l]) longest[m] = l;
+    for (int m = 0; m < mates && ok; ++m) {
+        // reads covering position p (counted from 1): those of at least p bases -- a suffix sum of the lengths
+        std::vector<uint64_t> cover((size_t)longest[m] + 2, 0);
+        for (int l = longest[m]; l >= 1; --l) cover[(size_t)l] = cover[(size_t)l + 1] + R.len_hist[m][l];
+        for (int p = 1; p <= longest[m] && ok; ++p) ok = fprintf(fp, "pos5\t%d\t%d\t%llu\t%llu\n", m + 1, p, (ull)R.by_pos5[m][p - 1], (ull)cover[(size_t)p]) > 0;
+    }
+    for (int m = 0; m < mates && ok; ++m)
+        for (int p = 1; p <= longest[m] && ok; ++p) ok = fprintf(fp, "pos3\t%d\t%d\t%llu\n", m + 1, p, (ull)R.by_pos3[m][p - 1]) > 0;
+    for (int a = 0; a < 5 && ok; ++a)
+        for (int b = 0; b < 4 && ok; ++b) ok = fprintf(fp, "subst\t%c\t%c\t%llu\n", "ACGTN"[a], "ACGT"[b], (ull)R.subst[a][b]) > 0;
+    for (int q = 0; q < 3 && ok; ++q) ok = fprintf(fp, "qual\t%s\t%llu\n", q == 0 ? "low" : (q == 1 ? "high" : "none"), (ull)R.by_qual[q]) > 0;
+    for (int c = 0; c <= RC_REPORT_MAX_PER_READ && ok; ++c) {
+        if (!R.per_read[c]) continue;
+        if (c < RC_REPORT_MAX_PER_READ)
+            ok = fprintf(fp, "perread\t%d\t%llu\n", c, (ull)R.per_read[c]) > 0;
+        else
+            ok = fprintf(fp, "perread\t%d+\t%llu\n", c, (ull)R.per_read[c]) > 0;
+    }
+    return fclose(fp) == 0 && ok;
+}
+
 void quality_histograms(const Block &b, int lpr, size_t room, std::vector<int32_t> &fh, std::vector<int32_t> &lh, int *total)
 {
     static char qbuf[MAX_READ_LENGTH];  // Reads::qual, reused from record to record

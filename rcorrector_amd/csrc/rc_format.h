@@ -154,6 +154,12 @@ void put_transcript(std::vector<char> &out, const Job &J, const Arena &A, size_t
 
 // a k-mer count spectrum as `jellyfish histo` prints it: "<count> <frequency>\n" per non-zero bin, ascending; false: not written
 bool write_histo(const char *path, const std::vector<uint64_t> &freq);
+// the correction report (rcorrector_amd.h: rc_change_report) as tab-separated text, one fact per line, the first field naming
+// the section; mates are written 1 and 2 (mate 2 only with two_mates), positions count from 1:
+//   reads <mate> <reads> <with changes> <unfixable> / changes <mate> <count> / pos5 <mate> <position> <changes> <reads covering it>
+//   and pos3 <mate> <distance from the last base, 1 = the last base> <changes>, a line per position up to the mate's longest
+//   read / subst <A|C|G|T|N> <A|C|G|T> <count>, all 20 / qual <low|high|none> <count> / perread <n | 64+> <reads>, non-zero ones
+bool write_change_report(const char *path, const rc_change_report &R, bool two_mates);
 // GetBadQuality's two histograms over the records of one block (main.cpp:88-128), at most `room` of them
 void quality_histograms(const Block &b, int lpr, size_t room, std::vector<int32_t> &fh, std::vector<int32_t> &lh, int *total);
 

@@ -134,6 +134,13 @@ struct rc_ctx {
     uint32_t rec_bin = 0;
     std::mutex rec_mutex;
     rc_ctx *lane_parent = nullptr;  // a slot lane: the context whose slots it serves
+    // correction report (rc_change_report_begin): the accumulator, RC_REPORT_WORDS 64-bit counts laid out as rc_change_report
+    // (nullptr: not armed; the batches of this context's slot lanes add to it too: lane_parent).  In the context a batch RUNS
+    // in (a lane included): the copy of its arena taken before the first correction kernel (grow-only), and where that copy
+    // of the batch launched last lies (nullptr: none was taken) -- all on that context's one compute stream
+    unsigned long long *rep_acc = nullptr;
+    rc_dbuf rep_snap;
+    const uint8_t *rep_snap_cur = nullptr;
 
     // batch scratch
     rc_dbuf counts;   // int32 per arena byte
@@ -252,6 +259,13 @@ int rc_launch_single(rc_ctx *ctx, const rc_device_batch_args &a, bool *ran);
 int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbytes, bool *done);
 int rc_launch_summary(rc_ctx *ctx, const int32_t *d_ret, uint32_t n);
 int rc_launch_kmer_info(rc_ctx *ctx, const rc_device_batch_args &a);
+
+// rc_report.hip: the correction report.  RC_REPORT_WORDS: 64-bit counts of an rc_change_report (8 per-mate totals, six
+// tables of 1024, 20 substitutions, 3 quality classes, 65 per-read bins)
+#define RC_REPORT_WORDS (8 + 6 * 1024 + 20 + 3 + 65)
+// every read of the batch against d_snap (the arena before correction, at the arena's alignment modulo 16), counted into d_out
+int rc_launch_change_report(rc_ctx *ctx, const rc_device_batch_args &a, const uint8_t *d_snap, unsigned long long *d_out);
+int rc_launch_report_commit(rc_ctx *ctx, const unsigned long long *d_staged, unsigned long long *d_out);
 
 // rc_transport.hip: the packed boundary (include/rcorrector_amd.h: rc_packed_batch)
 int rc_launch_unpack(rc_ctx *ctx, const uint32_t *d_packed, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, const uint32_t *d_exc_pos,

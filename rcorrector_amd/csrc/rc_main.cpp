@@ -23,6 +23,8 @@
 // spectrum of every k-mer counted, singletons included; with -c that of the dump's entries.
 // -histo-after FILE writes the spectrum of the CORRECTED reads in the same format (a recount session, rcorrector_amd.h:
 // rc_recount_begin) and adds one line to stderr: how many of their k-mers the table does not hold.
+// -report FILE writes the correction report (rcorrector_amd.h: rc_change_report; rc_format.h: write_change_report): the
+// substitutions by position, letters, quality class, mate and read, counted on the GPU as the batches complete.
 #include <fcntl.h>
 #include <malloc.h>
 #include <sys/stat.h>
@@ -63,6 +65,9 @@ static void print_help()
             "\t-histo-after STRING: also write the k-mer count spectrum of the corrected reads (same format, -histo-max bounds it too) and\n"
             "\t\treport how many of their k-mers the table does not hold; the corrected bases stay in GPU memory until the end of the run\n"
             "\t\t(one byte per base); with -gpus above 1 they are counted on the first GPU, from the corrected text the host holds\n"
+            "\t-report STRING: also write the correction report, tab-separated text: reads, changed bases by position from either end,\n"
+            "\t\tby substitution, by quality class and per read, for each mate; counted on the GPU as the batches complete; with -gpus\n"
+            "\t\tabove 1 every GPU keeps a report of its own and the file holds their sum\n"
             "\t-verbose-iter INT: threshold iterations recorded per read for -verbose (default: 64)\n");
 }
 
@@ -75,7 +80,7 @@ int main(int argc, char **argv)
     std::vector<ReadFile> &files = run.files, &mates = run.mates;
     int max_fix_per_k = 4, i;
     double wk = 0.95;
-    const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr;
+    const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr, *report = nullptr;
     long histo_max = 10000;
     std::string od = "./";
     bool verbose = false;
@@ -131,6 +136,8 @@ int main(int argc, char **argv)
             histo_max = atol(argv[++i]);
         else if (!strcmp("-histo-after", argv[i]))
             histo_after = argv[++i];
+        else if (!strcmp("-report", argv[i]))
+            report = argv[++i];
         else if (!strcmp("-packed", argv[i]))
             g_packed = true;
         else if (!strcmp("-h", argv[i])) {
@@ -475,6 +482,11 @@ int main(int argc, char **argv)
         }
     }
 
+    // -report: every context counts the batches that complete on it, whatever the transport
+    if (report)
+        for (int c = 0; c < nctx; ++c)
+            if (rc_change_report_begin(ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+
     // pipeline: reader (this thread) -> `inflight` workers per GPU -> writer thread (input order)
     warm.join();
     stamp("batch buffers ready");
@@ -508,6 +520,19 @@ int main(int argc, char **argv)
     if (g_timing)
         fprintf(stderr, "[rc timing] blocked: reader %.2f s (no free slot), workers %.2f s (no batch), writer %.2f s (next batch not done)\n", g_w_reader, g_w_worker, g_w_writer);
     fprintf(stderr, "Processed %llu reads\n\tCorrected %llu bases.\n", (unsigned long long)run.total_reads, (unsigned long long)run.total_cor);
+    if (report) {  // the contexts' reports, added up
+        std::vector<rc_change_report> part(1), sum(1);
+        memset(&sum[0], 0, sizeof sum[0]);
+        for (int c = 0; c < nctx; ++c) {
+            if (rc_change_report_get(ctx[c], &part[0])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+            const uint64_t *src = reinterpret_cast<const uint64_t *>(&part[0]);
+            uint64_t *dst = reinterpret_cast<uint64_t *>(&sum[0]);
+            for (size_t w = 0; w < sizeof(rc_change_report) / sizeof(uint64_t); ++w) dst[w] += src[w];
+        }
+        bool two_mates = false;
+        for (const ReadFile &f : files) two_mates = two_mates || f.paired || f.interleaved;
+        if (!write_change_report(report, sum[0], two_mates)) die("rcorrector: could not write %s\n", report);
+    }
     if (histo_after) {
         const double th0 = now_s();
         std::vector<uint64_t> freq((size_t)histo_max + 1);
