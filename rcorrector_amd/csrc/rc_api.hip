@@ -138,7 +138,7 @@ rc_ctx *rc_slot_lane(rc_ctx *ctx, int slot, bool create, bool refresh)
         ln->P = ctx->P;
         ln->params_set = ctx->params_set;
         ln->qual_bits = ctx->qual_bits;
-        ln->kept_arenas = ctx->kept_arenas;  // (descriptors only: the chunks stay the parent's)
+        ln->kept.arenas = ctx->kept.arenas;  // (descriptors only: the chunks stay the parent's)
         ln->profile = ctx->profile;          // measurement follows the batch into its lane (rc_profile_get adds the lanes up)
         ln->phase_prof = ctx->phase_prof;
         ln->phase_prof_print = ctx->phase_prof_print;
@@ -230,7 +230,7 @@ void rc_destroy(rc_ctx *c)
     rc_ctx_full *ctx = static_cast<rc_ctx_full *>(c);
     for (rc_ctx *&ln : ctx->lane) {  // (they borrow this context's table and arenas: they go first)
         if (ln) {
-            ln->kept_arenas.clear();
+            ln->kept.arenas.clear();
             rc_destroy(ln);
         }
         ln = nullptr;
@@ -260,9 +260,8 @@ void rc_destroy(rc_ctx *c)
     }
     if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
     if (ctx->s_d2h) (void)hipStreamDestroy(ctx->s_d2h);
-    for (auto &a : ctx->cnt_chunks)
-        if (a.p) (void)hipFree(a.p);
-    rc_kept_release(ctx);
+    ctx->cnt.release();
+    ctx->kept.release();
     rc_recount_release(ctx);
     rc_report_release(ctx);
     rc_table_release(ctx);

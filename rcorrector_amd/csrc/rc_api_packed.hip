@@ -330,9 +330,9 @@ int rc_submit_resident(rc_ctx *c, rc_resident_batch *b, int slot)
         rc_set_error(ctx, "submit_resident: %s mode needs an even number of reads", b->mode == 1 ? "paired" : "interleaved");
         return RC_ERR_ARG;
     }
-    const size_t n_kept = ctx->kept_arenas.size();
+    const size_t n_kept = ctx->kept.arenas.size();
     auto in_range = [&](int idx, uint64_t begin, uint64_t bytes) {
-        return idx >= 0 && (size_t)idx < n_kept && begin <= ctx->kept_arenas[(size_t)idx].bytes && bytes <= ctx->kept_arenas[(size_t)idx].bytes - begin;
+        return idx >= 0 && (size_t)idx < n_kept && begin <= ctx->kept.arenas[(size_t)idx].bytes && bytes <= ctx->kept.arenas[(size_t)idx].bytes - begin;
     };
     if (!in_range(b->arena_a, b->begin_a, b->bytes_a) || (b->mode == 1 && !in_range(b->arena_b, b->begin_b, b->bytes_b))) {
         rc_set_error(ctx, "submit_resident: no such range of a kept arena (%zu kept; rc_table_count_keep before counting)", n_kept);
@@ -401,8 +401,8 @@ int rc_submit_resident(rc_ctx *c, rc_resident_batch *b, int slot)
     RC_CHECK_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.e_h2d, 0));
     // the batch's own arena: its ranges of the kept arenas, side by side
     uint8_t *d_seq = (uint8_t *)sl.d_seq.p;
-    const uint8_t *orig_a = (const uint8_t *)ctx->kept_arenas[(size_t)b->arena_a].p + b->begin_a;
-    const uint8_t *orig_b = bytes_b ? (const uint8_t *)ctx->kept_arenas[(size_t)b->arena_b].p + b->begin_b : nullptr;
+    const uint8_t *orig_a = (const uint8_t *)ctx->kept.arenas[(size_t)b->arena_a].p + b->begin_a;
+    const uint8_t *orig_b = bytes_b ? (const uint8_t *)ctx->kept.arenas[(size_t)b->arena_b].p + b->begin_b : nullptr;
     if (b->bytes_a) RC_CHECK_HIP(ctx, hipMemcpyAsync(d_seq, orig_a, b->bytes_a, hipMemcpyDeviceToDevice, ctx->stream));
     if (bytes_b) RC_CHECK_HIP(ctx, hipMemcpyAsync(d_seq + b->bytes_a, orig_b, bytes_b, hipMemcpyDeviceToDevice, ctx->stream));
     if (!h_qb) RC_CHECK_HIP(ctx, hipMemsetAsync(sl.d_qual.p, 0, nbytes, ctx->stream));  // FASTA: qual[0] == 0 (Reads.h:224-266)

@@ -434,8 +434,8 @@ int rc_table_count_keep(rc_ctx *ctx, int on)
 int rc_table_count_arenas(const rc_ctx *ctx, size_t *n_arenas, uint64_t *bytes, size_t cap)
 {
     if (!ctx || !n_arenas) return RC_ERR_ARG;
-    *n_arenas = ctx->kept_arenas.size();
-    for (size_t i = 0; bytes && i < cap && i < ctx->kept_arenas.size(); ++i) bytes[i] = ctx->kept_arenas[i].bytes;
+    *n_arenas = ctx->kept.arenas.size();
+    for (size_t i = 0; bytes && i < cap && i < ctx->kept.arenas.size(); ++i) bytes[i] = ctx->kept.arenas[i].bytes;
     return RC_OK;
 }
 
@@ -447,9 +447,9 @@ int rc_table_count_release(rc_ctx *ctx)
     for (rc_ctx *ln : ctx->lane) {  // the slot lanes hold copies of the descriptors and run on streams of their own
         if (!ln) continue;
         RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream));
-        ln->kept_arenas.clear();
+        ln->kept.arenas.clear();
     }
-    rc_kept_release(ctx);
+    ctx->kept.release();
     return RC_OK;
 }
 

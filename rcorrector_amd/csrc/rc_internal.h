@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "rc_correct_core.h"
@@ -46,6 +47,23 @@ struct rc_dev_tmp {
 struct rc_dbuf {
     void *p = nullptr;
     size_t bytes = 0;
+};
+
+// the reads of a counting session in HBM: the arenas handed over, views into a few large allocations (chunks: a hipMalloc /
+// hipFree per arena -- dozens per run, each a round trip through the kernel driver -- cost more than counting them on a busy host)
+struct rc_ctx;
+struct rc_arena_set {
+    std::vector<rc_dbuf> arenas, chunks;
+    size_t chunk_used = 0;  // bytes of the last chunk handed out
+    size_t total = 0;       // bytes of reads
+    void release();
+    // a copy of an arena (device or host memory) into the set, on stream st; complete on return.  Errors go to ctx, as `what`
+    int keep(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_device, hipStream_t st, const char *what);
+    void move_to(rc_arena_set &to)  // `to` holds what this set held, this set nothing
+    {
+        to.release();
+        std::swap(*this, to);
+    }
 };
 
 #define RC_MAX_SLOTS 4
@@ -109,17 +127,12 @@ struct rc_ctx {
     rc_dbuf trace;
 
     // k-mer counter (rc_table_count_begin/add/finish): the arenas handed over so far, kept in HBM until finish
-    // (the arenas are views into a few large allocations, cnt_chunks: a hipMalloc / hipFree per arena -- dozens per run, each
-    // a round trip through the kernel driver -- cost more than counting them on a busy host)
-    std::vector<rc_dbuf> cnt_arenas;
-    std::vector<rc_dbuf> cnt_chunks;
-    size_t cnt_chunk_used = 0;  // bytes of the last chunk handed out
-    size_t cnt_total = 0;  // bytes
+    rc_arena_set cnt;
     bool cnt_active = false;
     // rc_table_count_keep(on): finish() leaves the arenas here instead of releasing them -- the reads of a data set
     // that was counted on this GPU are corrected where they lie (rc_submit_resident)
     bool cnt_keep = false;
-    std::vector<rc_dbuf> kept_arenas, kept_chunks;
+    rc_arena_set kept;
     // k-mer count spectrum of the counter (rc_table_count_spectrum): the bound finish() bins to (0 = off), and what the last
     // finish (on ctxs[0] of a sharded one) saw -- freq[bound + 1], then distinct, total, unique, max_count; empty: none
     // since the last count_begin
@@ -128,8 +141,7 @@ struct rc_ctx {
     // recount session (rc_recount_begin): a second counting session that builds no table -- its arenas in chunks of its own
     // (the counter's and the kept arenas are never touched), the bound its spectrum is binned to, and whether the batches
     // that complete on this context (its slot lanes included: lane_parent) append their corrected arena (rc_recount_follow)
-    std::vector<rc_dbuf> rec_arenas, rec_chunks;
-    size_t rec_chunk_used = 0, rec_total = 0;
+    rc_arena_set rec;
     bool rec_active = false, rec_follow = false;
     uint32_t rec_bin = 0;
     std::mutex rec_mutex;
@@ -200,25 +212,15 @@ int rc_build_table_from_device_pairs(rc_ctx *ctx, const uint64_t *d_canon, const
 int rc_launch_canonicalize(rc_ctx *ctx, uint64_t *d_codes, size_t n);
 int rc_launch_lookup(rc_ctx *ctx, const uint64_t *d_codes, size_t n, int32_t *d_out);
 int rc_launch_probe(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int32_t *d_counts);
-int rc_count_begin(rc_ctx *ctx);
-void rc_kept_release(rc_ctx *ctx);
-int rc_count_add(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_device);
-int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers);
-int rc_count_park(rc_ctx *ctx);
-int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers);
-int rc_count_reads(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int min_count, int64_t *n_kmers);
 int rc_launch_selftest_bound(rc_ctx *ctx, const int32_t *d_c, size_t n, double e, int32_t *d_oi, double *d_od);
 int rc_launch_export(rc_ctx *ctx, uint64_t *d_codes, int32_t *d_counts, unsigned long long *d_n, size_t cap);
 // k-mer count spectrum (rc_device.h: rc_spec_add): the table's into host arrays freq[max_bin + 1], st[4]; one slice's run-length
 // counts added to d_out (freq[max_bin + 1], then the four statistics; zeroed by the caller) on stream st
 int rc_table_spectrum_scan(rc_ctx *ctx, uint32_t max_bin, uint64_t *freq, uint64_t *st);
 int rc_launch_spectrum_counts(rc_ctx *ctx, hipStream_t st, const uint32_t *d_cnt, size_t n, uint32_t max_bin, unsigned long long *d_out);
-// recount session: begin / append a copy of an arena (on stream st; complete on return) / the passes and the census kernel
-// (out: freq[rec_bin + 1], distinct, total, unique, max_count, absent_distinct, absent_total) / release (also on every error)
-int rc_recount_begin_session(rc_ctx *ctx, uint32_t max_bin);
-int rc_recount_append(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_device, hipStream_t st);
-int rc_recount_finish_session(rc_ctx *ctx, std::vector<uint64_t> *out);
-void rc_recount_release(rc_ctx *ctx);
+// one sorted slice of a recount session (distinct codes and their counts) against the table, added to d_out (max_bin + 1 + 6
+// uint64: the spectrum's, then absent_distinct, absent_total; zeroed by the caller) on stream st
+int rc_launch_census(rc_ctx *ctx, hipStream_t st, const uint64_t *d_uniq, const uint32_t *d_cnt, size_t n, uint32_t max_bin, unsigned long long *d_out);
 int rc_table_entries_in_dump_order(rc_ctx *ctx, std::vector<uint64_t> *codes, std::vector<int32_t> *counts);
 int rc_error_rate_candidates(rc_ctx *ctx, const uint64_t *d_codes, size_t n, bool by_hash, size_t want, std::vector<uint64_t> *vals);
 int rc_table_codes_device(rc_ctx *ctx, uint64_t **d_codes, size_t *n);
@@ -232,6 +234,20 @@ int rc_launch_probe_tier(rc_ctx *ctx, const struct rc_device_batch_args &a, size
 int rc_launch_compact(rc_ctx *ctx, const uint8_t *d_cls, uint32_t n, uint32_t *d_list, size_t stride, uint32_t *d_count);
 int rc_launch_compact_local(rc_ctx *ctx, const uint8_t *d_cls, uint32_t n, uint32_t *d_list, size_t stride, uint32_t *d_count);
 int rc_launch_compact_flag(rc_ctx *ctx, const uint8_t *d_flag, uint32_t n, uint32_t *d_list, size_t stride, uint32_t *d_count);
+
+// rc_count.hip
+int rc_count_begin(rc_ctx *ctx);
+int rc_count_add(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_device);
+int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers);
+int rc_count_park(rc_ctx *ctx);
+int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers);
+int rc_count_reads(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int min_count, int64_t *n_kmers);
+// recount session: begin / append a copy of an arena (on stream st; complete on return) / the passes and the census kernel
+// (out: freq[rec_bin + 1], distinct, total, unique, max_count, absent_distinct, absent_total) / release (also on every error)
+int rc_recount_begin_session(rc_ctx *ctx, uint32_t max_bin);
+int rc_recount_append(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_device, hipStream_t st);
+int rc_recount_finish_session(rc_ctx *ctx, std::vector<uint64_t> *out);
+void rc_recount_release(rc_ctx *ctx);
 
 // rc_correct.hip
 #define RC_TIER_ALL 0x7fffffff  // rc_kernel_args::tier_hi: no length tiers

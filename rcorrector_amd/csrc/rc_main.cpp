@@ -469,7 +469,7 @@ int main(int argc, char **argv)
         uint64_t hbm_free = 0;
         if (rc_device_memory(ctx[0], &hbm_free, nullptr)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
         if (const char *hf = getenv("RC_HBM_FREE_MB")) hbm_free = (uint64_t)atoll(hf) << 20;  // tests: as if this much were free
-        const uint64_t scratch = std::min<uint64_t>(count_mem, bases * 46);  // (the passes' scratch: rc_table.hip, 40 bytes per k-mer occurrence + 15 %)
+        const uint64_t scratch = std::min<uint64_t>(count_mem, bases * 46);  // (the passes' scratch: rc_count.hip, 40 bytes per k-mer occurrence + 15 %)
         const uint64_t need = bases + scratch + ((uint64_t)256 << 20);
         if ((known || bases) && need > hbm_free)
             die("rcorrector: -histo-after keeps the corrected bases in GPU memory until the end of the run: about %llu MB with the counting scratch, "

@@ -1,8 +1,8 @@
 // rc_table.hip -- the k-mer count table in HBM (Store.h:17-88 re-designed for the MI355X memory
 // system) and the kernels that touch only the table: build (K0), lookup, the per-batch probe
-// kernel (K1: reads -> counts[], ErrorCorrection.cpp:716-723), k-mer counting from reads
-// (stages 0-2 of run_rcorrector.pl:262-281) and the last-base-variant pass of the ERROR_RATE
-// estimation (main.cpp:329-345).
+// kernel (K1: reads -> counts[], ErrorCorrection.cpp:716-723), the k-mer count spectrum and
+// census, and the last-base-variant pass of the ERROR_RATE estimation (main.cpp:329-345).  The
+// k-mer counter that feeds the build (stages 0-2 of run_rcorrector.pl:262-281) is rc_count.hip.
 //
 // Layout: open addressing over 64-byte buckets (one HBM/L2 sector per probe): 5 slots of
 // {key_lo, key_hi, count} + one meta dword.  A key lives in its home bucket hash(key) & mask or,
@@ -710,6 +710,71 @@ int rc_table_spectrum_scan(rc_ctx *ctx, uint32_t max_bin, uint64_t *freq, uint64
     return RC_OK;
 }
 
+// ---- census of a recount session (rc_count.hip: rc_recount_finish_session hands every sorted slice to it) ---------------------
+#define RC_CENSUS_UNROLL 2
+
+// Per lane one distinct canonical code of a sorted slice and its count: is the code in the table (GetCount != 0), and the
+// count into the spectrum (rc_spec_add, as k_spectrum_counts).  The codes are sorted by value, the table is addressed by
+// hash, so every probe is a scattered 64-byte bucket read.  What round 6 learnt about such reads (docs/rounds/r6.md,
+// tools/microbench_bucket.hip): their cost is the number of load INSTRUCTIONS times the lines each touches, not the bytes
+// -- so the probe is rc_table_lookup_quad (a quad reads a bucket together: four instructions of 16 lines for four buckets
+// instead of four of 64), and a lane keeps RC_CENSUS_UNROLL codes, eight such loads, in flight: with 16 waves a CU that is
+// 128 outstanding instructions, where the microbenchmark's rate out of a table beyond the L2 no longer rose.
+// out = freq[max_bin + 1], {distinct, total, unique, max_count}, {absent_distinct, absent_total}
+__global__ __launch_bounds__(RC_SPEC_THREADS) void k_census(rc_table_view T, const uint64_t *__restrict__ uniq, const uint32_t *__restrict__ cnt, size_t n,
+                                                            uint32_t max_bin, uint32_t lds_bins, unsigned long long *__restrict__ out)
+{
+    __shared__ uint32_t s_small[RC_SPEC_WAVES * RC_SPEC_SMALL];
+    extern __shared__ uint32_t s_big[];
+    rc_spec_zero(s_small, s_big, lds_bins);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t *s_wave = s_small + w * RC_SPEC_SMALL;
+    rc_spec_acc A;
+    unsigned long long absent_distinct = 0;  // wave-uniform (ballot counts)
+    unsigned long long absent_total = 0;     // per lane
+    const size_t per_wave = 64 * RC_CENSUS_UNROLL, stride = (size_t)gridDim.x * RC_SPEC_WAVES * per_wave;
+    for (size_t base = ((size_t)blockIdx.x * RC_SPEC_WAVES + w) * per_wave; base < n; base += stride) {  // (wave-uniform: the quad lookup wants every lane)
+        uint64_t key[RC_CENSUS_UNROLL];
+        uint32_t c[RC_CENSUS_UNROLL];
+        int in_table[RC_CENSUS_UNROLL];
+#pragma unroll
+        for (int u = 0; u < RC_CENSUS_UNROLL; ++u) {
+            const size_t i = base + (size_t)u * 64 + lane;
+            key[u] = i < n ? uniq[i] : 0;
+            c[u] = i < n ? cnt[i] : 0;  // (a run length is at least 1: 0 = no code for this lane)
+        }
+#pragma unroll
+        for (int u = 0; u < RC_CENSUS_UNROLL; ++u) in_table[u] = rc_table_lookup_quad<true>(T, key[u], c[u] != 0);
+#pragma unroll
+        for (int u = 0; u < RC_CENSUS_UNROLL; ++u) {
+            const bool valid = c[u] != 0, absent = valid && in_table[u] == 0;
+            rc_spec_add(A, valid, c[u], max_bin, lds_bins, s_wave, s_big, out);
+            absent_distinct += (unsigned long long)__popcll(__ballot(absent));
+            if (absent) absent_total += c[u];
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) absent_total += __shfl_xor(absent_total, o, 64);
+    if (lane == 0 && absent_distinct) {  // one atomic per wavefront and quantity
+        atomicAdd(&out[(size_t)max_bin + 5], absent_distinct);
+        atomicAdd(&out[(size_t)max_bin + 6], absent_total);
+    }
+    rc_spec_flush(A, max_bin, lds_bins, s_small, s_big, out);
+}
+
+// d_out: max_bin + 1 + 6 uint64, zeroed by the caller before the first launch; adds one slice (stream st)
+int rc_launch_census(rc_ctx *ctx, hipStream_t st, const uint64_t *d_uniq, const uint32_t *d_cnt, size_t n, uint32_t max_bin, unsigned long long *d_out)
+{
+    if (n == 0) return RC_OK;
+    const uint32_t lds = rc_spec_lds_bins(max_bin);
+    const size_t bytes = rc_spec_lds_bytes(lds);
+    RC_CHECK_HIP(ctx, rc_spec_allow_lds(reinterpret_cast<const void *>(k_census), bytes));
+    const size_t per_block = (size_t)RC_SPEC_WAVES * 64 * RC_CENSUS_UNROLL;
+    const unsigned G = (unsigned)std::min<size_t>(RC_SPEC_MAX_BLOCKS, (n + per_block - 1) / per_block);
+    hipLaunchKernelGGL(k_census, dim3(G), dim3(RC_SPEC_THREADS), bytes, st, rc_view(ctx), d_uniq, d_cnt, n, max_bin, lds, d_out);
+    RC_CHECK_HIP(ctx, hipGetLastError());
+    return RC_OK;
+}
+
 __global__ void k_dump_order_keys(const uint64_t *__restrict__ codes, size_t n, uint64_t *__restrict__ keys)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1317,962 +1382,4 @@ int rc_launch_probe(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int32_t *d
     rc_timer_end(ctx, RC_T_PROBE);
     RC_CHECK_HIP(ctx, hipGetLastError());
     return RC_OK;
-}
-
-// ---- exact k-mer counter in bounded memory (stages 0-2 of run_rcorrector.pl:262-281 for reads that are, or
-// pass through, HBM).  `jellyfish bc` + `count --bc` exist so that the singletons of a data set -- most of its
-// distinct k-mers once reads carry errors -- never occupy the counter (run_rcorrector.pl:262-273).  Here the same
-// end is reached by cutting the KEY SPACE instead: the arenas handed over are kept in HBM (one byte per base:
-// 100 M x 150 bp are 15 GB of 288), and finish() makes P passes over them; pass p looks only at the k-mers whose
-// hash falls into slice p of P -- emit -> radix sort -> run-length encode -> keep count >= min_count -- so that no
-// more than 1/P of the k-mer occurrences is ever in flight, whatever share of them are singletons.  A histogram
-// pass sizes the slices; P follows from the memory the passes may use (RC_COUNT_MEM_MB, default 24 GiB).  The result
-// is what `jellyfish count -C` + `dump -L 2` hands to the reference: every canonical k-mer with its exact count.
-__global__ void k_u32_to_i32_clamped(const uint32_t *in, int32_t *out, size_t n)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[i] > 0x7fffffffu ? 0x7fffffff : (int32_t)in[i];
-}
-
-__device__ __forceinline__ uint32_t rc_count_slice(uint64_t key, uint32_t P)
-{
-    return (uint32_t)(((uint64_t)rc_hash(key ^ 0x9E3779B97F4A7C15ull) * P) >> 32);
-}
-
-// MODE 0: hist[slice] += valid k-mers of the tile; MODE 1: the canonical codes of slice `p` are appended to out
-template <int MODE>
-__global__ __launch_bounds__(RC_PROBE_THREADS) void k_count_scan(const uint8_t *__restrict__ seq, size_t nbytes, int k, uint32_t P, uint32_t p,
-                                                                 unsigned long long *__restrict__ hist, uint64_t *__restrict__ out,
-                                                                 unsigned long long *__restrict__ cursor)
-{
-    __shared__ uint32_t s_code[RC_PROBE_TILE / 16 + 4];
-    __shared__ uint16_t s_inv[RC_PROBE_TILE / 16 + 4];
-    __shared__ uint32_t s_hist[64];
-    const size_t tile0 = (size_t)blockIdx.x * RC_PROBE_TILE;
-    const int t = threadIdx.x;
-    if (MODE == 0 && t < 64) s_hist[t] = 0;
-    for (int chunk = t; chunk < RC_PROBE_TILE / 16 + 2; chunk += RC_PROBE_THREADS) {
-        const size_t g = tile0 + (size_t)chunk * 16;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (g + 16 <= nbytes) {
-            v = *reinterpret_cast<const uint4 *>(seq + g);
-        } else if (g < nbytes) {
-            uint32_t w[4] = {0, 0, 0, 0};
-            for (size_t j = 0; g + j < nbytes; ++j) w[j >> 2] |= (uint32_t)seq[g + j] << (8 * (j & 3));
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        uint32_t code, inv, nul;
-        rc_pack16(v, code, inv, nul);
-        s_code[chunk] = code;
-        s_inv[chunk ^ 1] = (uint16_t)inv;  // NUL is also "not ACGT"
-    }
-    if (t < 2) s_code[RC_PROBE_TILE / 16 + 2 + t] = 0xFFFFFFFFu;
-    __syncthreads();
-    const uint32_t *m_inv = reinterpret_cast<const uint32_t *>(s_inv);
-    // the canonical code of the window at tile position a, if it is a k-mer of a read, and its slice
-    auto window = [&](int a, uint64_t &key, uint32_t &sl) -> bool {
-        const size_t g = tile0 + (size_t)a;
-        if (g + (size_t)k > nbytes) return false;
-        const int mw = a >> 5, ms = a & 31;
-        const uint64_t invw = (((uint64_t)m_inv[mw] << 32) | m_inv[mw + 1]) << ms;
-        if (invw >> (64 - k)) return false;
-        const int cw = a >> 4, cs = 2 * (a & 15);
-        uint64_t x = ((uint64_t)s_code[cw] << 32) | s_code[cw + 1];
-        if (cs) x = (x << cs) | ((uint64_t)s_code[cw + 2] >> (32 - cs));
-        key = rc_canonical(x >> (64 - 2 * k), k);
-        sl = rc_count_slice(key, P);
-        return true;
-    };
-    constexpr int ITER = RC_PROBE_TILE / RC_PROBE_THREADS, WAVES = RC_PROBE_THREADS / 64;
-    if (MODE == 0) {
-        for (int it = 0; it < ITER; ++it) {
-            uint64_t key;
-            uint32_t sl;
-            if (window(it * RC_PROBE_THREADS + t, key, sl)) atomicAdd(&s_hist[sl & 63u], 1u);  // (P <= 64)
-        }
-        __syncthreads();
-        if (t < 64 && s_hist[t]) atomicAdd(hist + t, (unsigned long long)s_hist[t]);
-        return;
-    }
-    // MODE 1: ONE atomic on the output cursor per workgroup (one word sustains ~90 atomics per microsecond; a wave-level
-    // reservation is 60 times as many): count the keys of slice p per (iteration, wave), reserve, then write
-    __shared__ uint32_t s_n[ITER * WAVES + 1];
-    __shared__ unsigned long long s_base;
-    const int wv = t >> 6, lane = t & 63;
-    for (int it = 0; it < ITER; ++it) {
-        uint64_t key;
-        uint32_t sl;
-        const bool take = window(it * RC_PROBE_THREADS + t, key, sl) && sl == p;
-        const unsigned long long m = __ballot(take);
-        if (lane == 0) s_n[it * WAVES + wv] = (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    if (t == 0) {
-        uint32_t run = 0;
-        for (int i = 0; i < ITER * WAVES; ++i) {
-            const uint32_t c = s_n[i];
-            s_n[i] = run;
-            run += c;
-        }
-        s_base = run ? atomicAdd(cursor, (unsigned long long)run) : 0ull;
-    }
-    __syncthreads();
-    const unsigned long long base = s_base;
-    for (int it = 0; it < ITER; ++it) {
-        uint64_t key = 0;
-        uint32_t sl;
-        const bool take = window(it * RC_PROBE_THREADS + t, key, sl) && sl == p;
-        const unsigned long long m = __ballot(take);
-        if (take) out[base + s_n[it * WAVES + wv] + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull))] = key;
-    }
-}
-
-__global__ void k_flag_keep(const uint64_t *__restrict__ uniq, const uint32_t *__restrict__ cnt, size_t n, int min_count,
-                            uint8_t *__restrict__ keep)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) keep[i] = cnt[i] >= (uint32_t)min_count ? 1 : 0;
-}
-
-static void rc_count_release(rc_ctx *ctx)
-{
-    for (auto &a : ctx->cnt_chunks)
-        if (a.p) (void)hipFree(a.p);
-    ctx->cnt_chunks.clear();
-    ctx->cnt_chunk_used = 0;
-    ctx->cnt_arenas.clear();
-    ctx->cnt_total = 0;
-}
-
-void rc_kept_release(rc_ctx *ctx)
-{
-    for (auto &a : ctx->kept_chunks)
-        if (a.p) (void)hipFree(a.p);
-    ctx->kept_chunks.clear();
-    ctx->kept_arenas.clear();
-}
-
-int rc_count_begin(rc_ctx *ctx)
-{
-    if (ctx->rec_active) {
-        rc_set_error(ctx, "count_begin: a recount session is open (rc_recount_finish it first)");
-        return RC_ERR_STATE;
-    }
-    rc_count_release(ctx);
-    rc_kept_release(ctx);
-    ctx->spec_counted.clear();
-    ctx->cnt_active = true;
-    return RC_OK;
-}
-
-// an arena's place in a session's chunks (behind the last one in the current chunk, 256-byte aligned with 64 bytes of slack, or
-// a new chunk) and its copy there on stream `st`, complete when this returns: the caller's buffer is its own again
-static int rc_arena_keep(rc_ctx *ctx, std::vector<rc_dbuf> &arenas, std::vector<rc_dbuf> &chunks, size_t &chunk_used, size_t &total, const uint8_t *seq,
-                         size_t nbytes, bool from_device, hipStream_t st, const char *what)
-{
-    const size_t need = (nbytes + 64 + 255) & ~(size_t)255, chunk_bytes = (size_t)2 << 30;
-    if (chunks.empty() || chunk_used + need > chunks.back().bytes) {
-        rc_dbuf c;
-        c.bytes = need > chunk_bytes ? need : chunk_bytes;
-        RC_CHECK_HIP(ctx, hipMalloc(&c.p, c.bytes));
-        chunks.push_back(c);
-        chunk_used = 0;
-    }
-    rc_dbuf a;
-    a.p = (char *)chunks.back().p + chunk_used;
-    a.bytes = nbytes;
-    hipError_t e = hipMemcpyAsync(a.p, seq, nbytes, from_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);  // (the caller's buffer is its own again when this returns)
-    if (e != hipSuccess) {
-        rc_set_error(ctx, "%s: copy failed: %s", what, hipGetErrorString(e));
-        return RC_ERR_HIP;
-    }
-    chunk_used += need;
-    arenas.push_back(a);
-    total += nbytes;
-    return RC_OK;
-}
-
-// what a session may keep in HBM
-static size_t rc_count_retain_cap()
-{
-    size_t cap = (size_t)128 << 30;
-    if (const char *e = getenv("RC_COUNT_RETAIN_MB")) cap = (size_t)atoll(e) << 20;
-    return cap;
-}
-
-// keeps a copy of the arena in HBM (from_device: d_seq is device memory, else host memory)
-int rc_count_add(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_device)
-{
-    if (!ctx->cnt_active) {
-        rc_set_error(ctx, "count_add: call rc_table_count_begin first");
-        return RC_ERR_STATE;
-    }
-    if (nbytes == 0) return RC_OK;
-    if (nbytes >= (1ull << 32)) {
-        rc_set_error(ctx, "count: an arena must be below 2^32 bytes (add it in pieces)");
-        return RC_ERR_ARG;
-    }
-    const size_t cap = rc_count_retain_cap();
-    if (ctx->cnt_total + nbytes > cap) {
-        rc_set_error(ctx, "count: %zu MB of reads exceed what the k-mer counter keeps in HBM (%zu MB, RC_COUNT_RETAIN_MB): count them with "
-                          "jellyfish and pass the dump (-c)", (ctx->cnt_total + nbytes) >> 20, cap >> 20);
-        return RC_ERR_NOMEM;
-    }
-    return rc_arena_keep(ctx, ctx->cnt_arenas, ctx->cnt_chunks, ctx->cnt_chunk_used, ctx->cnt_total, seq, nbytes, from_device, ctx->stream, "count_add");
-}
-
-// ---- the pass loop both finishes share (rc_count_finish: the table; rc_recount_finish: the census of a recount session) -----
-// One key slice, sorted and run-length encoded, as a pass hands it to its consumer: `runs` distinct canonical codes in uniq
-// (ascending) with their counts in cnt.  keys_s, keep, d_runs and tmp are the pass's scratch, free for the consumer; all of it
-// is overwritten by the next pass, which the stream orders behind what the consumer queued.
-struct rc_count_pass {
-    uint32_t p, P;
-    const unsigned long long *hist;  // k-mer occurrences per slice
-    unsigned long long occ_total;
-    const uint64_t *uniq;
-    const uint32_t *cnt;
-    size_t runs;
-    uint64_t *keys_s;  // max_slice codes
-    uint8_t *keep;     // max_slice bytes
-    size_t *d_runs;
-    void *tmp;         // rocPRIM scratch: enough for a sort, a run-length encode or a select of max_slice items
-    size_t tmp_bytes;
-};
-// where the passes spent their time (t_sort / t_rle: with RC_COUNT_TIMING's extra synchronisations)
-struct rc_count_times {
-    uint32_t P = 0;
-    double alloc = 0, emit = 0, sort = 0, rle = 0;
-};
-
-// histogram -> P passes over `arenas` (total_bytes of reads): emit slice p's canonical codes -> radix sort -> run-length
-// encode -> consume(pass).  Returns with the stream drained.
-template <class F>
-static int rc_count_passes(rc_ctx *ctx, const std::vector<rc_dbuf> &arenas, size_t total_bytes, bool timing, rc_count_times &T, F &&consume)
-{
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const int k = ctx->k;
-    // passes: a pass holds, per k-mer occurrence of its slice, the key (8 B), its sorted copy (8 B), the sort's scratch
-    // (~8 B) and the run-length output (8 + 4 + 1 B)
-    size_t mem = (size_t)24 << 30;
-    if (const char *e = getenv("RC_COUNT_MEM_MB")) mem = (size_t)atoll(e) << 20;
-    const double per_occ = 40.0;
-    uint32_t P = (uint32_t)((double)total_bytes * per_occ * 1.15 / (double)mem) + 1;
-    if (P > 64) P = 64;
-    T.P = P;
-    rc_dev_tmp b_hist, b_cursor;
-    RC_CHECK_HIP(ctx, b_hist.alloc(64 * 8));
-    RC_CHECK_HIP(ctx, b_cursor.alloc(8));
-    RC_CHECK_HIP(ctx, hipMemsetAsync(b_hist.p, 0, 64 * 8, ctx->stream));
-    for (const auto &a : arenas) {
-        const unsigned G = (unsigned)((a.bytes + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
-        hipLaunchKernelGGL(k_count_scan<0>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, (const uint8_t *)a.p, a.bytes, k, P, 0u,
-                           b_hist.as<unsigned long long>(), (uint64_t *)nullptr, (unsigned long long *)nullptr);
-    }
-    RC_CHECK_HIP(ctx, hipGetLastError());
-    unsigned long long hist[64];
-    RC_CHECK_HIP(ctx, hipMemcpyAsync(hist, b_hist.p, sizeof hist, hipMemcpyDeviceToHost, ctx->stream));
-    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    size_t max_slice = 0;
-    for (uint32_t p = 0; p < P; ++p) max_slice = std::max(max_slice, (size_t)hist[p]);
-    if (max_slice >= (1ull << 32)) {
-        rc_set_error(ctx, "count: a pass of %zu k-mer occurrences exceeds 2^32 (lower RC_COUNT_MEM_MB for more passes)", max_slice);
-        return RC_ERR_ARG;
-    }
-    if (max_slice == 0) return RC_OK;
-    // One allocation holds the passes' scratch.  (Round 3 allocated per pass and concatenated at the end: some forty
-    // hipMalloc / hipFree calls, each a round trip through the kernel driver -- 0.1 s on a quiet host, 0.5 s and more on a
-    // busy one, against 0.2 s for the counting itself.)
-    size_t ts_sort = 0, ts_rle = 0, ts_sel = 0;
-    RC_CHECK_HIP(ctx, rocprim::radix_sort_keys(nullptr, ts_sort, (uint64_t *)nullptr, (uint64_t *)nullptr, max_slice, 0, 2 * k > 64 ? 64 : 2 * k, ctx->stream));
-    RC_CHECK_HIP(ctx, rocprim::run_length_encode(nullptr, ts_rle, (uint64_t *)nullptr, (unsigned int)max_slice, (uint64_t *)nullptr, (uint32_t *)nullptr,
-                                                 (size_t *)nullptr, ctx->stream));
-    RC_CHECK_HIP(ctx, rocprim::select(nullptr, ts_sel, (uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t *)nullptr, (size_t *)nullptr, max_slice, ctx->stream));
-    const size_t tmp_bytes = std::max(ts_sort, std::max(ts_rle, ts_sel));
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_keys = 0, o_keys_s = o_keys + up(max_slice * 8), o_cnt = o_keys_s + up(max_slice * 8), o_keep = o_cnt + up(max_slice * 4),
-                 o_runs = o_keep + up(max_slice), o_tmp = o_runs + 256, pool_bytes = o_tmp + up(tmp_bytes);
-    rc_dev_tmp b_pool;
-    const double ta0 = now();
-    RC_CHECK_HIP(ctx, b_pool.alloc(pool_bytes));
-    T.alloc += now() - ta0;
-    char *pool = b_pool.as<char>();
-    uint64_t *keys = (uint64_t *)(pool + o_keys), *keys_s = (uint64_t *)(pool + o_keys_s);
-    uint32_t *cnt = (uint32_t *)(pool + o_cnt);
-    uint8_t *keep = (uint8_t *)(pool + o_keep);
-    size_t *d_runs = (size_t *)(pool + o_runs);
-    void *tmp = pool + o_tmp;
-    unsigned long long occ_total = 0;
-    for (uint32_t p = 0; p < P; ++p) occ_total += hist[p];
-    for (uint32_t p = 0; p < P; ++p) {
-        const size_t m = (size_t)hist[p];
-        if (m == 0) continue;
-        RC_CHECK_HIP(ctx, hipMemsetAsync(b_cursor.p, 0, 8, ctx->stream));
-        for (const auto &a : arenas) {
-            const unsigned G = (unsigned)((a.bytes + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
-            hipLaunchKernelGGL(k_count_scan<1>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, (const uint8_t *)a.p, a.bytes, k, P, p,
-                               (unsigned long long *)nullptr, keys, b_cursor.as<unsigned long long>());
-        }
-        RC_CHECK_HIP(ctx, hipGetLastError());
-        double tp = now();
-        if (timing) {
-            RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            T.emit += now() - tp;
-            tp = now();
-        }
-        size_t t1 = tmp_bytes;
-        RC_CHECK_HIP(ctx, rocprim::radix_sort_keys(tmp, t1, keys, keys_s, m, 0, 2 * k > 64 ? 64 : 2 * k, ctx->stream));
-        if (timing) {
-            RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            T.sort += now() - tp;
-            tp = now();
-        }
-        t1 = tmp_bytes;
-        RC_CHECK_HIP(ctx, rocprim::run_length_encode(tmp, t1, keys_s, (unsigned int)m, keys, cnt, d_runs, ctx->stream));
-        size_t runs = 0;
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(&runs, d_runs, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
-        RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        T.rle += now() - tp;
-        if (runs == 0) continue;
-        const rc_count_pass pass = {p, P, hist, occ_total, keys, cnt, runs, keys_s, keep, d_runs, tmp, tmp_bytes};
-        const int rc = consume(pass);
-        if (rc) return rc;
-    }
-    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RC_OK;
-}
-
-int rc_count_finish(rc_ctx *ctx, int min_count, int64_t *n_kmers)
-{
-    if (!ctx->cnt_active) {
-        rc_set_error(ctx, "count_finish: call rc_table_count_begin first");
-        return RC_ERR_STATE;
-    }
-    ctx->cnt_active = false;
-    // RC_COUNT_TIMING=1 (dev): where finish() spends its time, on stderr
-    static const bool timing = getenv("RC_COUNT_TIMING") != nullptr;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
-    rc_count_times T;
-    double t_sel = 0;  // (with the synchronisations the selection needs anyway)
-    struct release_on_exit {
-        rc_ctx *c;
-        ~release_on_exit() { rc_count_release(c); }  // (an error leaves nothing behind; success with cnt_keep has moved the arenas out)
-    } guard{ctx};
-    // rc_table_count_spectrum: every slice's run-length counts, before the min_count filter, into one device array
-    const uint32_t spec_bin = ctx->spec_arm;
-    rc_dev_tmp b_spec;
-    if (spec_bin) {
-        RC_CHECK_HIP(ctx, b_spec.alloc(((size_t)spec_bin + 5) * 8));
-        RC_CHECK_HIP(ctx, hipMemsetAsync(b_spec.p, 0, ((size_t)spec_bin + 5) * 8, ctx->stream));
-    }
-    // The kept entries of all passes go straight into the two arrays the table is built from.  Their number is known only
-    // at the end: the arrays are sized from the first pass that keeps anything (its share of the occurrences, + 15 %) and
-    // regrown in the rare case a later pass does not fit.
-    rc_dev_tmp b_allk, b_allc;
-    size_t total_kept = 0, cap_kept = 0;
-    const int prc = rc_count_passes(ctx, ctx->cnt_arenas, ctx->cnt_total, timing, T, [&](const rc_count_pass &s) -> int {
-        const size_t runs = s.runs;
-        const double tp = now();
-        if (spec_bin) {
-            const int rs = rc_launch_spectrum_counts(ctx, ctx->stream, s.cnt, runs, spec_bin, b_spec.as<unsigned long long>());
-            if (rs) return rs;
-        }
-        hipLaunchKernelGGL(k_flag_keep, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, ctx->stream, s.uniq, s.cnt, runs, min_count, s.keep);
-        // the kept keys land in keys_s (free again) and are copied out; their counts go through a second select into the
-        // same buffer and from there, clamped to int32, to their place
-        size_t t1 = s.tmp_bytes;
-        RC_CHECK_HIP(ctx, rocprim::select(s.tmp, t1, s.uniq, s.keep, s.keys_s, s.d_runs, runs, ctx->stream));
-        size_t nsel = 0;
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(&nsel, s.d_runs, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
-        RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        t_sel += now() - tp;
-        if (nsel == 0) return RC_OK;
-        if (total_kept + nsel > cap_kept) {
-            const double ta1 = now();
-            // what this pass kept of its occurrences, applied to the occurrences still to come
-            unsigned long long seen = 0;
-            for (uint32_t q = 0; q <= s.p; ++q) seen += s.hist[q];
-            const double per_occ_kept = (double)(total_kept + nsel) / (double)(seen ? seen : 1);
-            size_t want = (size_t)(per_occ_kept * (double)s.occ_total * (cap_kept ? 1.5 : 1.15)) + ((size_t)1 << 20);
-            static const bool tight = getenv("RC_COUNT_TIGHT") != nullptr;  // tests: no slack, every pass regrows the arrays
-            if (want < total_kept + nsel || tight) want = total_kept + nsel;
-            rc_dev_tmp nk, nc;
-            RC_CHECK_HIP(ctx, nk.alloc((want + 1) * 8));
-            RC_CHECK_HIP(ctx, nc.alloc((want + 1) * 4));
-            if (total_kept) {
-                RC_CHECK_HIP(ctx, hipMemcpyAsync(nk.p, b_allk.p, total_kept * 8, hipMemcpyDeviceToDevice, ctx->stream));
-                RC_CHECK_HIP(ctx, hipMemcpyAsync(nc.p, b_allc.p, total_kept * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            }
-            std::swap(nk.p, b_allk.p);
-            std::swap(nc.p, b_allc.p);
-            cap_kept = want;
-            T.alloc += now() - ta1;
-        }
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(b_allk.as<uint64_t>() + total_kept, s.keys_s, nsel * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        uint32_t *selc = reinterpret_cast<uint32_t *>(s.keys_s);  // (keys_s was copied out: the stream orders the reuse)
-        t1 = s.tmp_bytes;
-        RC_CHECK_HIP(ctx, rocprim::select(s.tmp, t1, s.cnt, s.keep, selc, s.d_runs, runs, ctx->stream));
-        hipLaunchKernelGGL(k_u32_to_i32_clamped, dim3((unsigned)((nsel + 255) / 256)), dim3(256), 0, ctx->stream, selc, b_allc.as<int32_t>() + total_kept, nsel);
-        RC_CHECK_HIP(ctx, hipGetLastError());
-        total_kept += nsel;
-        return RC_OK;
-    });
-    if (prc) return prc;
-    if (spec_bin) {
-        std::vector<uint64_t> f((size_t)spec_bin + 5);
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(f.data(), b_spec.p, f.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->spec_counted = std::move(f);
-    }
-    if (!b_allk.p) {  // nothing kept: the build still wants its two arrays
-        RC_CHECK_HIP(ctx, b_allk.alloc(8));
-        RC_CHECK_HIP(ctx, b_allc.alloc(4));
-    }
-    if (ctx->cnt_keep) {  // the reads stay where they are for rc_submit_resident
-        ctx->kept_arenas.swap(ctx->cnt_arenas);
-        ctx->kept_chunks.swap(ctx->cnt_chunks);
-        ctx->cnt_chunk_used = 0;
-        ctx->cnt_total = 0;
-    }
-    const double t_passes = now();
-    rc_count_release(ctx);  // the reads are no longer needed: their memory goes to the table build
-    const double t_concat = now();
-    int rc = rc_build_table_from_device_pairs(ctx, b_allk.as<uint64_t>(), b_allc.as<int32_t>(), total_kept);
-    if (timing)
-        fprintf(stderr, "[rc count timing] finish %.3f s: histogram + %u passes %.3f (emit %.3f, sort %.3f, run lengths %.3f, select %.3f, hipMalloc %.3f), reads released %.3f, table build %.3f\n",
-                now() - t_begin, T.P, t_passes - t_begin, T.emit, T.sort, T.rle, t_sel, T.alloc, t_concat - t_passes, now() - t_concat);
-    if (rc != RC_OK) rc_kept_release(ctx);
-    if (rc == RC_OK && total_kept) {  // (rc_estimate_error_rate takes them from here; rc_table_release frees them)
-        ctx->counted_codes = b_allk.p;
-        ctx->counted_n = total_kept;
-        b_allk.p = nullptr;
-    }
-    if (n_kmers) *n_kmers = (int64_t)total_kept;
-    return rc;
-}
-
-// ---- recount session (include/rcorrector_amd.h: rc_recount_begin): a second, read-only use of the counter ------------------
-// The session's arenas live in chunks of their own (rec_chunks), so neither the counter's session nor the kept arenas are
-// touched; finish() runs the shared pass loop over them and hands every slice to the census kernel instead of the table build.
-#define RC_CENSUS_UNROLL 2
-
-// Per lane one distinct canonical code of a sorted slice and its count: is the code in the table (GetCount != 0), and the
-// count into the spectrum (rc_spec_add, as k_spectrum_counts).  The codes are sorted by value, the table is addressed by
-// hash, so every probe is a scattered 64-byte bucket read.  What round 6 learnt about such reads (docs/rounds/r6.md,
-// tools/microbench_bucket.hip): their cost is the number of load INSTRUCTIONS times the lines each touches, not the bytes
-// -- so the probe is rc_table_lookup_quad (a quad reads a bucket together: four instructions of 16 lines for four buckets
-// instead of four of 64), and a lane keeps RC_CENSUS_UNROLL codes, eight such loads, in flight: with 16 waves a CU that is
-// 128 outstanding instructions, where the microbenchmark's rate out of a table beyond the L2 no longer rose.
-// out = freq[max_bin + 1], {distinct, total, unique, max_count}, {absent_distinct, absent_total}
-__global__ __launch_bounds__(RC_SPEC_THREADS) void k_census(rc_table_view T, const uint64_t *__restrict__ uniq, const uint32_t *__restrict__ cnt, size_t n,
-                                                            uint32_t max_bin, uint32_t lds_bins, unsigned long long *__restrict__ out)
-{
-    __shared__ uint32_t s_small[RC_SPEC_WAVES * RC_SPEC_SMALL];
-    extern __shared__ uint32_t s_big[];
-    rc_spec_zero(s_small, s_big, lds_bins);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t *s_wave = s_small + w * RC_SPEC_SMALL;
-    rc_spec_acc A;
-    unsigned long long absent_distinct = 0;  // wave-uniform (ballot counts)
-    unsigned long long absent_total = 0;     // per lane
-    const size_t per_wave = 64 * RC_CENSUS_UNROLL, stride = (size_t)gridDim.x * RC_SPEC_WAVES * per_wave;
-    for (size_t base = ((size_t)blockIdx.x * RC_SPEC_WAVES + w) * per_wave; base < n; base += stride) {  // (wave-uniform: the quad lookup wants every lane)
-        uint64_t key[RC_CENSUS_UNROLL];
-        uint32_t c[RC_CENSUS_UNROLL];
-        int in_table[RC_CENSUS_UNROLL];
-#pragma unroll
-        for (int u = 0; u < RC_CENSUS_UNROLL; ++u) {
-            const size_t i = base + (size_t)u * 64 + lane;
-            key[u] = i < n ? uniq[i] : 0;
-            c[u] = i < n ? cnt[i] : 0;  // (a run length is at least 1: 0 = no code for this lane)
-        }
-#pragma unroll
-        for (int u = 0; u < RC_CENSUS_UNROLL; ++u) in_table[u] = rc_table_lookup_quad<true>(T, key[u], c[u] != 0);
-#pragma unroll
-        for (int u = 0; u < RC_CENSUS_UNROLL; ++u) {
-            const bool valid = c[u] != 0, absent = valid && in_table[u] == 0;
-            rc_spec_add(A, valid, c[u], max_bin, lds_bins, s_wave, s_big, out);
-            absent_distinct += (unsigned long long)__popcll(__ballot(absent));
-            if (absent) absent_total += c[u];
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) absent_total += __shfl_xor(absent_total, o, 64);
-    if (lane == 0 && absent_distinct) {  // one atomic per wavefront and quantity
-        atomicAdd(&out[(size_t)max_bin + 5], absent_distinct);
-        atomicAdd(&out[(size_t)max_bin + 6], absent_total);
-    }
-    rc_spec_flush(A, max_bin, lds_bins, s_small, s_big, out);
-}
-
-// d_out: max_bin + 1 + 6 uint64, zeroed by the caller before the first launch; adds one slice (stream st)
-static int rc_launch_census(rc_ctx *ctx, hipStream_t st, const uint64_t *d_uniq, const uint32_t *d_cnt, size_t n, uint32_t max_bin, unsigned long long *d_out)
-{
-    if (n == 0) return RC_OK;
-    const uint32_t lds = rc_spec_lds_bins(max_bin);
-    const size_t bytes = rc_spec_lds_bytes(lds);
-    RC_CHECK_HIP(ctx, rc_spec_allow_lds(reinterpret_cast<const void *>(k_census), bytes));
-    const size_t per_block = (size_t)RC_SPEC_WAVES * 64 * RC_CENSUS_UNROLL;
-    const unsigned G = (unsigned)std::min<size_t>(RC_SPEC_MAX_BLOCKS, (n + per_block - 1) / per_block);
-    hipLaunchKernelGGL(k_census, dim3(G), dim3(RC_SPEC_THREADS), bytes, st, rc_view(ctx), d_uniq, d_cnt, n, max_bin, lds, d_out);
-    RC_CHECK_HIP(ctx, hipGetLastError());
-    return RC_OK;
-}
-
-void rc_recount_release(rc_ctx *ctx)
-{
-    for (auto &a : ctx->rec_chunks)
-        if (a.p) (void)hipFree(a.p);
-    ctx->rec_chunks.clear();
-    ctx->rec_arenas.clear();
-    ctx->rec_chunk_used = 0;
-    ctx->rec_total = 0;
-    ctx->rec_active = false;
-}
-
-int rc_recount_begin_session(rc_ctx *ctx, uint32_t max_bin)
-{
-    rc_recount_release(ctx);  // (a session that was never finished)
-    ctx->rec_bin = max_bin;
-    ctx->rec_active = true;
-    return RC_OK;
-}
-
-// a copy of the arena into the session's chunks, on stream `st` of the session's device (a slot lane's for the batches it ran)
-int rc_recount_append(rc_ctx *ctx, const uint8_t *seq, size_t nbytes, bool from_device, hipStream_t st)
-{
-    if (nbytes == 0) return RC_OK;
-    if (nbytes >= (1ull << 32)) {
-        rc_set_error(ctx, "recount: an arena must be below 2^32 bytes (add it in pieces)");
-        return RC_ERR_ARG;
-    }
-    std::lock_guard<std::mutex> lock(ctx->rec_mutex);  // (batches of several slots may complete on threads of their own)
-    const size_t cap = rc_count_retain_cap();
-    int rc = RC_OK;
-    if (ctx->rec_total + nbytes > cap) {
-        rc_set_error(ctx, "recount: %zu MB of reads exceed what a counting session keeps in HBM (%zu MB, RC_COUNT_RETAIN_MB)", (ctx->rec_total + nbytes) >> 20, cap >> 20);
-        rc = RC_ERR_NOMEM;
-    } else {
-        rc = rc_arena_keep(ctx, ctx->rec_arenas, ctx->rec_chunks, ctx->rec_chunk_used, ctx->rec_total, seq, nbytes, from_device, st, "recount_add");
-    }
-    if (rc) rc_recount_release(ctx);  // an error ends the session and leaves nothing allocated
-    return rc;
-}
-
-// out: freq[rec_bin + 1], then distinct, total, unique, max_count, absent_distinct, absent_total
-int rc_recount_finish_session(rc_ctx *ctx, std::vector<uint64_t> *out)
-{
-    static const bool timing = getenv("RC_COUNT_TIMING") != nullptr;
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
-    struct release_on_exit {
-        rc_ctx *c;
-        ~release_on_exit() { rc_recount_release(c); }  // (success or error: the session is over, nothing stays allocated)
-    } guard{ctx};
-    const uint32_t max_bin = ctx->rec_bin;
-    const size_t words = (size_t)max_bin + 7;
-    rc_dev_tmp b_out;
-    RC_CHECK_HIP(ctx, b_out.alloc(words * 8));
-    RC_CHECK_HIP(ctx, hipMemsetAsync(b_out.p, 0, words * 8, ctx->stream));
-    rc_count_times T;
-    double t_census = 0;
-    const int prc = rc_count_passes(ctx, ctx->rec_arenas, ctx->rec_total, timing, T, [&](const rc_count_pass &s) -> int {
-        const double tp = now();
-        const int rc = rc_launch_census(ctx, ctx->stream, s.uniq, s.cnt, s.runs, max_bin, b_out.as<unsigned long long>());
-        if (rc == RC_OK && timing) {
-            RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            t_census += now() - tp;
-        }
-        return rc;
-    });
-    if (prc) return prc;
-    out->assign(words, 0);
-    RC_CHECK_HIP(ctx, hipMemcpyAsync(out->data(), b_out.p, words * 8, hipMemcpyDeviceToHost, ctx->stream));
-    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (timing)
-        fprintf(stderr, "[rc recount timing] finish %.3f s: histogram + %u passes over %zu MB (emit %.3f, sort %.3f, run lengths %.3f, census %.3f, hipMalloc %.3f)\n",
-                now() - t_begin, T.P, ctx->rec_total >> 20, T.emit, T.sort, T.rle, t_census, T.alloc);
-    return RC_OK;
-}
-
-// n bytes from device memory of one GPU to device memory of another (or the same), queued on `st`, a stream of the destination's
-// device, which is the current one: device to device, peer to peer where the GPUs can, else through the host (synchronous)
-static int rc_copy_across(rc_ctx *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t n, hipStream_t st)
-{
-    if (n == 0) return RC_OK;
-    const bool force_staged = getenv("RC_REPLICATE_STAGED") != nullptr;  // tests: the path of GPUs without peer access
-    if (dst_dev == src_dev && !force_staged) {
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, st));
-        return RC_OK;
-    }
-    int can = 0;
-    if (!force_staged && dst_dev != src_dev) {
-        if (hipDeviceCanAccessPeer(&can, dst_dev, src_dev) != hipSuccess) can = 0;
-        if (can) {
-            const hipError_t e = hipDeviceEnablePeerAccess(src_dev, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) can = 0;
-            (void)hipGetLastError();
-        }
-    }
-    if (can) {
-        RC_CHECK_HIP(ctx, hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, n, st));
-        return RC_OK;
-    }
-    const size_t CH = (size_t)64 << 20;
-    char *h = nullptr;
-    RC_CHECK_HIP(ctx, hipHostMalloc((void **)&h, std::min(CH, n), hipHostMallocPortable));
-    hipError_t e = hipSuccess;
-    for (size_t at = 0; at < n && e == hipSuccess; at += CH) {
-        const size_t m = std::min(CH, n - at);
-        e = hipSetDevice(src_dev);
-        if (e == hipSuccess) e = hipMemcpy(h, (const char *)src + at, m, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipSetDevice(dst_dev);
-        if (e == hipSuccess) e = hipMemcpyAsync((char *)dst + at, h, m, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    (void)hipSetDevice(dst_dev);
-    (void)hipHostFree(h);
-    if (e != hipSuccess) {
-        rc_set_error(ctx, "count: copy between GPUs failed: %s", hipGetErrorString(e));
-        return RC_ERR_HIP;
-    }
-    return RC_OK;
-}
-
-// rc_count_finish for reads that are spread over n contexts, one per GPU (`rcorrector -gpus N` in one pass: a batch's bases
-// are uploaded to the GPU that will correct it, and nowhere else).  The key space is cut into the P slices one GPU would
-// use; slice p belongs to GPU p % n: every GPU emits that slice's keys from its own arenas and sends them to the owner,
-// which sorts, run-length encodes and selects them -- so each GPU scans a 1 / n share of the reads P times and sorts a
-// 1 / n share of the keys, and every occurrence crosses xGMI once.  The kept entries are put end to end in slice order on
-// cs[0], where the table is built: the same entries in the same order as rc_count_finish on one GPU holding all the reads
-// (the ERROR_RATE sample and the dump depend on that order).  cs[0]'s min_count / keep settings apply to all.
-int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers)
-{
-    rc_ctx *c0 = cs[0];
-    for (int g = 0; g < n; ++g) {
-        if (!cs[g] || !cs[g]->cnt_active) {
-            rc_set_error(c0, "count_finish_sharded: every context needs an open counting session (rc_table_count_begin)");
-            return RC_ERR_STATE;
-        }
-        if (cs[g]->k != c0->k) {
-            rc_set_error(c0, "count_finish_sharded: contexts must have the same k");
-            return RC_ERR_ARG;
-        }
-        for (int h = 0; h < g; ++h)
-            if (cs[h] == cs[g]) {
-                rc_set_error(c0, "count_finish_sharded: a context is listed twice");
-                return RC_ERR_ARG;
-            }
-    }
-    struct release_all {
-        rc_ctx **cs;
-        int n;
-        ~release_all()
-        {
-            for (int g = 0; g < n; ++g) {
-                (void)hipSetDevice(cs[g]->device);
-                cs[g]->cnt_active = false;
-                rc_count_release(cs[g]);  // (success with cnt_keep has moved the arenas out)
-            }
-            (void)hipSetDevice(cs[0]->device);
-        }
-    } guard{cs, n};
-    const int k = c0->k;
-    size_t total = 0;
-    for (int g = 0; g < n; ++g) total += cs[g]->cnt_total;
-    size_t mem = (size_t)24 << 30;
-    if (const char *e = getenv("RC_COUNT_MEM_MB")) mem = (size_t)atoll(e) << 20;
-    uint32_t P = (uint32_t)((double)total * 40.0 * 1.15 / (double)mem) + 1;  // (as rc_count_finish: the entries come out in the same order)
-    if (P > 64) P = 64;
-    auto fail_hip = [&](hipError_t e, const char *what) {
-        rc_set_error(c0, "count_finish_sharded: %s failed: %s", what, hipGetErrorString(e));
-        return RC_ERR_HIP;
-    };
-#define RC_SH_HIP(call, what)                        \
-    do {                                             \
-        const hipError_t e__ = (call);               \
-        if (e__ != hipSuccess) return fail_hip(e__, what); \
-    } while (0)
-    // histograms: occurrences per slice on every GPU
-    std::vector<std::vector<unsigned long long>> hist((size_t)n, std::vector<unsigned long long>(64, 0));
-    {
-        std::vector<rc_dev_tmp> b_hist((size_t)n);
-        for (int g = 0; g < n; ++g) {
-            RC_SH_HIP(hipSetDevice(cs[g]->device), "hipSetDevice");
-            RC_SH_HIP(b_hist[(size_t)g].alloc(64 * 8), "hipMalloc");
-            RC_SH_HIP(hipMemsetAsync(b_hist[(size_t)g].p, 0, 64 * 8, cs[g]->stream), "hipMemsetAsync");
-            for (const auto &a : cs[g]->cnt_arenas) {
-                const unsigned G = (unsigned)((a.bytes + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
-                hipLaunchKernelGGL(k_count_scan<0>, dim3(G), dim3(RC_PROBE_THREADS), 0, cs[g]->stream, (const uint8_t *)a.p, a.bytes, k, P, 0u,
-                                   b_hist[(size_t)g].as<unsigned long long>(), (uint64_t *)nullptr, (unsigned long long *)nullptr);
-            }
-            RC_SH_HIP(hipGetLastError(), "histogram launch");
-            RC_SH_HIP(hipMemcpyAsync(hist[(size_t)g].data(), b_hist[(size_t)g].p, 64 * 8, hipMemcpyDeviceToHost, cs[g]->stream), "hipMemcpyAsync");
-        }
-        for (int g = 0; g < n; ++g) {
-            RC_SH_HIP(hipSetDevice(cs[g]->device), "hipSetDevice");
-            RC_SH_HIP(hipStreamSynchronize(cs[g]->stream), "hipStreamSynchronize");
-        }
-    }
-    std::vector<size_t> slice_total(P, 0);
-    for (uint32_t p = 0; p < P; ++p)
-        for (int g = 0; g < n; ++g) slice_total[p] += (size_t)hist[(size_t)g][p];
-    // per owner: the scratch of its largest slice; per GPU: a staging buffer for the keys it emits for someone else
-    struct Owner {
-        rc_dev_tmp pool, allk, allc, spec;
-        size_t max_slice = 0, tmp_bytes = 0, kept = 0, cap = 0;
-        size_t o_keys_s = 0, o_cnt = 0, o_keep = 0, o_runs = 0, o_tmp = 0;
-    };
-    std::vector<Owner> own((size_t)n);
-    std::vector<rc_dev_tmp> stage((size_t)n), cursor((size_t)n);
-    std::vector<size_t> stage_each((size_t)n, 0);
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const uint32_t spec_bin = c0->spec_arm;
-    for (int g = 0; g < n; ++g) {
-        Owner &O = own[(size_t)g];
-        size_t max_emit = 0;
-        for (uint32_t p = 0; p < P; ++p) {
-            if ((int)(p % (uint32_t)n) == g) O.max_slice = std::max(O.max_slice, slice_total[p]);
-            else max_emit = std::max(max_emit, (size_t)hist[(size_t)g][p]);
-        }
-        if (O.max_slice >= (1ull << 32)) {
-            rc_set_error(c0, "count: a pass of %zu k-mer occurrences exceeds 2^32 (lower RC_COUNT_MEM_MB for more passes)", O.max_slice);
-            return RC_ERR_ARG;
-        }
-        RC_SH_HIP(hipSetDevice(cs[g]->device), "hipSetDevice");
-        RC_SH_HIP(cursor[(size_t)g].alloc((size_t)n * 8), "hipMalloc");  // one cursor and one staging buffer per owner of a round
-        stage_each[(size_t)g] = max_emit;
-        if (max_emit) RC_SH_HIP(stage[(size_t)g].alloc((size_t)n * max_emit * 8), "hipMalloc");
-        if (O.max_slice == 0) continue;
-        size_t ts_sort = 0, ts_rle = 0, ts_sel = 0;
-        RC_SH_HIP(rocprim::radix_sort_keys(nullptr, ts_sort, (uint64_t *)nullptr, (uint64_t *)nullptr, O.max_slice, 0, 2 * k > 64 ? 64 : 2 * k, cs[g]->stream), "sort size");
-        RC_SH_HIP(rocprim::run_length_encode(nullptr, ts_rle, (uint64_t *)nullptr, (unsigned int)O.max_slice, (uint64_t *)nullptr, (uint32_t *)nullptr, (size_t *)nullptr,
-                                             cs[g]->stream), "rle size");
-        RC_SH_HIP(rocprim::select(nullptr, ts_sel, (uint64_t *)nullptr, (uint8_t *)nullptr, (uint64_t *)nullptr, (size_t *)nullptr, O.max_slice, cs[g]->stream), "select size");
-        O.tmp_bytes = std::max(ts_sort, std::max(ts_rle, ts_sel));
-        O.o_keys_s = up(O.max_slice * 8);
-        O.o_cnt = O.o_keys_s + up(O.max_slice * 8);
-        O.o_keep = O.o_cnt + up(O.max_slice * 4);
-        O.o_runs = O.o_keep + up(O.max_slice);
-        O.o_tmp = O.o_runs + 256;
-        RC_SH_HIP(O.pool.alloc(O.o_tmp + up(O.tmp_bytes)), "hipMalloc");
-        if (spec_bin) {  // (rc_table_count_spectrum on ctxs[0]: every owner sums the spectrum of its slices)
-            RC_SH_HIP(O.spec.alloc(((size_t)spec_bin + 5) * 8), "hipMalloc");
-            RC_SH_HIP(hipMemsetAsync(O.spec.p, 0, ((size_t)spec_bin + 5) * 8, cs[g]->stream), "hipMemsetAsync");
-        }
-    }
-    // rounds: in round r GPU o owns slice r n + o
-    struct Piece {
-        int owner;
-        size_t at, n;
-    };
-    std::vector<Piece> pieces(P, Piece{0, 0, 0});  // where slice p's kept entries lie in its owner's arrays
-    for (uint32_t r0 = 0; r0 < P; r0 += (uint32_t)n) {
-        // every GPU emits, for every owner of this round, the slice's keys from its own arenas: its own slice straight into its
-        // sort buffer, the others' into a staging buffer each -- all GPUs at once, nothing waits for the host
-        auto before_of = [&](int g, uint32_t p) {  // a GPU's keys follow those of the GPUs before it
-            size_t b = 0;
-            for (int h = 0; h < g; ++h) b += (size_t)hist[(size_t)h][p];
-            return b;
-        };
-        for (int g = 0; g < n; ++g) {
-            RC_SH_HIP(hipSetDevice(cs[g]->device), "hipSetDevice");
-            RC_SH_HIP(hipMemsetAsync(cursor[(size_t)g].p, 0, (size_t)n * 8, cs[g]->stream), "hipMemsetAsync");
-            for (int o = 0; o < n; ++o) {
-                const uint32_t p = r0 + (uint32_t)o;
-                if (p >= P) break;
-                if (hist[(size_t)g][p] == 0) continue;
-                uint64_t *dst_local = g == o ? own[(size_t)o].pool.as<uint64_t>() + before_of(g, p) : stage[(size_t)g].as<uint64_t>() + (size_t)o * stage_each[(size_t)g];
-                for (const auto &a : cs[g]->cnt_arenas) {
-                    const unsigned G = (unsigned)((a.bytes + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
-                    hipLaunchKernelGGL(k_count_scan<1>, dim3(G), dim3(RC_PROBE_THREADS), 0, cs[g]->stream, (const uint8_t *)a.p, a.bytes, k, P, p,
-                                       (unsigned long long *)nullptr, dst_local, cursor[(size_t)g].as<unsigned long long>() + o);
-                }
-                RC_SH_HIP(hipGetLastError(), "emit launch");
-            }
-        }
-        for (int g = 0; g < n; ++g) {
-            RC_SH_HIP(hipSetDevice(cs[g]->device), "hipSetDevice");
-            RC_SH_HIP(hipStreamSynchronize(cs[g]->stream), "hipStreamSynchronize");
-        }
-        // ... and every owner fetches what the others emitted for it (the owners' streams side by side)
-        for (int o = 0; o < n; ++o) {
-            const uint32_t p = r0 + (uint32_t)o;
-            if (p >= P) break;
-            RC_SH_HIP(hipSetDevice(cs[o]->device), "hipSetDevice");
-            for (int g = 0; g < n; ++g) {
-                const size_t m = (size_t)hist[(size_t)g][p];
-                if (g == o || m == 0) continue;
-                const int rc = rc_copy_across(c0, own[(size_t)o].pool.as<uint64_t>() + before_of(g, p), cs[o]->device,
-                                              stage[(size_t)g].as<uint64_t>() + (size_t)o * stage_each[(size_t)g], cs[g]->device, m * 8, cs[o]->stream);
-                if (rc) return rc;
-            }
-        }
-        for (int g = 0; g < n; ++g) {
-            RC_SH_HIP(hipSetDevice(cs[g]->device), "hipSetDevice");
-            RC_SH_HIP(hipStreamSynchronize(cs[g]->stream), "hipStreamSynchronize");
-        }
-        // every owner reduces its slice (the owners' streams run side by side; the host waits for each in turn)
-        std::vector<size_t> runs((size_t)n, 0), nsel((size_t)n, 0);
-        for (int phase = 0; phase < 3; ++phase)
-            for (int o = 0; o < n; ++o) {
-                const uint32_t p = r0 + (uint32_t)o;
-                if (p >= P || slice_total[p] == 0) continue;
-                Owner &O = own[(size_t)o];
-                const size_t m = slice_total[p];
-                char *pool = O.pool.as<char>();
-                uint64_t *keys = (uint64_t *)pool, *keys_s = (uint64_t *)(pool + O.o_keys_s);
-                uint32_t *cnt = (uint32_t *)(pool + O.o_cnt);
-                uint8_t *keep = (uint8_t *)(pool + O.o_keep);
-                size_t *d_runs = (size_t *)(pool + O.o_runs);
-                void *tmp = pool + O.o_tmp;
-                hipStream_t st = cs[o]->stream;
-                RC_SH_HIP(hipSetDevice(cs[o]->device), "hipSetDevice");
-                size_t t1 = O.tmp_bytes;
-                if (phase == 0) {
-                    RC_SH_HIP(rocprim::radix_sort_keys(tmp, t1, keys, keys_s, m, 0, 2 * k > 64 ? 64 : 2 * k, st), "sort");
-                    t1 = O.tmp_bytes;
-                    RC_SH_HIP(rocprim::run_length_encode(tmp, t1, keys_s, (unsigned int)m, keys, cnt, d_runs, st), "run lengths");
-                    RC_SH_HIP(hipMemcpyAsync(&runs[(size_t)o], d_runs, sizeof(size_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-                } else if (phase == 1) {
-                    RC_SH_HIP(hipStreamSynchronize(st), "hipStreamSynchronize");
-                    if (runs[(size_t)o] == 0) continue;
-                    if (spec_bin) {
-                        const int rs = rc_launch_spectrum_counts(c0, st, cnt, runs[(size_t)o], spec_bin, O.spec.as<unsigned long long>());
-                        if (rs) return rs;
-                    }
-                    hipLaunchKernelGGL(k_flag_keep, dim3((unsigned)((runs[(size_t)o] + 255) / 256)), dim3(256), 0, st, keys, cnt, runs[(size_t)o], min_count, keep);
-                    RC_SH_HIP(rocprim::select(tmp, t1, keys, keep, keys_s, d_runs, runs[(size_t)o], st), "select");
-                    RC_SH_HIP(hipMemcpyAsync(&nsel[(size_t)o], d_runs, sizeof(size_t), hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
-                } else {
-                    RC_SH_HIP(hipStreamSynchronize(st), "hipStreamSynchronize");
-                    const size_t ns = runs[(size_t)o] ? nsel[(size_t)o] : 0;
-                    pieces[p] = Piece{o, O.kept, ns};
-                    if (ns == 0) continue;
-                    if (O.kept + ns > O.cap) {  // (sized from what this owner has kept of what it has seen, + 50 %)
-                        size_t seen = 0, todo = 0;
-                        for (uint32_t q = (uint32_t)o; q < P; q += (uint32_t)n) (q <= p ? seen : todo) += slice_total[q];
-                        size_t want = (size_t)((double)(O.kept + ns) * (1.0 + 1.5 * (double)todo / (double)(seen ? seen : 1))) + ((size_t)1 << 16);
-                        static const bool tight = getenv("RC_COUNT_TIGHT") != nullptr;
-                        if (want < O.kept + ns || tight) want = O.kept + ns;
-                        rc_dev_tmp nk, nc;
-                        RC_SH_HIP(nk.alloc((want + 1) * 8), "hipMalloc");
-                        RC_SH_HIP(nc.alloc((want + 1) * 4), "hipMalloc");
-                        if (O.kept) {
-                            RC_SH_HIP(hipMemcpyAsync(nk.p, O.allk.p, O.kept * 8, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
-                            RC_SH_HIP(hipMemcpyAsync(nc.p, O.allc.p, O.kept * 4, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
-                            RC_SH_HIP(hipStreamSynchronize(st), "hipStreamSynchronize");
-                        }
-                        std::swap(nk.p, O.allk.p);
-                        std::swap(nc.p, O.allc.p);
-                        O.cap = want;
-                    }
-                    RC_SH_HIP(hipMemcpyAsync(O.allk.as<uint64_t>() + O.kept, keys_s, ns * 8, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
-                    uint32_t *selc = reinterpret_cast<uint32_t *>(keys_s);  // (keys_s was copied out: the stream orders the reuse)
-                    RC_SH_HIP(rocprim::select(tmp, t1, cnt, keep, selc, d_runs, runs[(size_t)o], st), "select");
-                    hipLaunchKernelGGL(k_u32_to_i32_clamped, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st, selc, O.allc.as<int32_t>() + O.kept, ns);
-                    RC_SH_HIP(hipGetLastError(), "launch");
-                    O.kept += ns;
-                }
-            }
-        for (int o = 0; o < n; ++o) {
-            RC_SH_HIP(hipSetDevice(cs[o]->device), "hipSetDevice");
-            RC_SH_HIP(hipStreamSynchronize(cs[o]->stream), "hipStreamSynchronize");
-        }
-    }
-    if (spec_bin) {  // every owner's few KB back to the host, summed (the slices are disjoint in key space)
-        std::vector<uint64_t> sum((size_t)spec_bin + 5, 0), f((size_t)spec_bin + 5);
-        for (int g = 0; g < n; ++g) {
-            if (!own[(size_t)g].spec.p) continue;
-            RC_SH_HIP(hipSetDevice(cs[g]->device), "hipSetDevice");
-            RC_SH_HIP(hipMemcpyAsync(f.data(), own[(size_t)g].spec.p, f.size() * 8, hipMemcpyDeviceToHost, cs[g]->stream), "hipMemcpyAsync");
-            RC_SH_HIP(hipStreamSynchronize(cs[g]->stream), "hipStreamSynchronize");
-            const size_t mc = (size_t)spec_bin + 4;  // (max_count: a maximum, the rest sums)
-            for (size_t i = 0; i < mc; ++i) sum[i] += f[i];
-            sum[mc] = std::max(sum[mc], f[mc]);
-            own[(size_t)g].spec.reset();
-        }
-        c0->spec_counted = std::move(sum);
-    }
-    // the kept entries, slice after slice, on cs[0]
-    size_t total_kept = 0;
-    for (uint32_t p = 0; p < P; ++p) total_kept += pieces[p].n;
-    RC_SH_HIP(hipSetDevice(c0->device), "hipSetDevice");
-    rc_dev_tmp b_allk, b_allc;
-    RC_SH_HIP(b_allk.alloc((total_kept + 1) * 8), "hipMalloc");
-    RC_SH_HIP(b_allc.alloc((total_kept + 1) * 4), "hipMalloc");
-    {
-        size_t at = 0;
-        for (uint32_t p = 0; p < P; ++p) {
-            const Piece &pc = pieces[p];
-            if (pc.n == 0) continue;
-            const Owner &O = own[(size_t)pc.owner];
-            int rc = rc_copy_across(c0, b_allk.as<uint64_t>() + at, c0->device, O.allk.as<uint64_t>() + pc.at, cs[pc.owner]->device, pc.n * 8, c0->stream);
-            if (!rc) rc = rc_copy_across(c0, b_allc.as<int32_t>() + at, c0->device, O.allc.as<int32_t>() + pc.at, cs[pc.owner]->device, pc.n * 4, c0->stream);
-            if (rc) return rc;
-            at += pc.n;
-        }
-        RC_SH_HIP(hipStreamSynchronize(c0->stream), "hipStreamSynchronize");
-    }
-    for (int g = 0; g < n; ++g) {  // scratch back to its device; the reads stay where they are for rc_submit_resident, if asked
-        RC_SH_HIP(hipSetDevice(cs[g]->device), "hipSetDevice");
-        own[(size_t)g].pool.reset();
-        own[(size_t)g].allk.reset();
-        own[(size_t)g].allc.reset();
-        stage[(size_t)g].reset();
-        cursor[(size_t)g].reset();
-        cs[g]->cnt_active = false;
-        if (c0->cnt_keep) {
-            cs[g]->kept_arenas.swap(cs[g]->cnt_arenas);
-            cs[g]->kept_chunks.swap(cs[g]->cnt_chunks);
-            cs[g]->cnt_chunk_used = 0;
-            cs[g]->cnt_total = 0;
-        }
-        rc_count_release(cs[g]);
-    }
-    RC_SH_HIP(hipSetDevice(c0->device), "hipSetDevice");
-    int rc = rc_build_table_from_device_pairs(c0, b_allk.as<uint64_t>(), b_allc.as<int32_t>(), total_kept);
-    if (rc != RC_OK)
-        for (int g = 0; g < n; ++g) {
-            (void)hipSetDevice(cs[g]->device);
-            rc_kept_release(cs[g]);
-        }
-    (void)hipSetDevice(c0->device);
-    if (rc == RC_OK && total_kept) {
-        c0->counted_codes = b_allk.p;
-        c0->counted_n = total_kept;
-        b_allk.p = nullptr;
-    }
-    if (n_kmers) *n_kmers = (int64_t)total_kept;
-#undef RC_SH_HIP
-    return rc;
-}
-
-// ends a counting session without counting: the arenas it was given become kept arenas (rc_submit_resident), no table is built
-int rc_count_park(rc_ctx *ctx)
-{
-    if (!ctx->cnt_active) {
-        rc_set_error(ctx, "count_park: call rc_table_count_begin first");
-        return RC_ERR_STATE;
-    }
-    ctx->cnt_active = false;
-    ctx->kept_arenas.swap(ctx->cnt_arenas);
-    ctx->kept_chunks.swap(ctx->cnt_chunks);
-    ctx->cnt_chunk_used = 0;
-    ctx->cnt_total = 0;
-    rc_count_release(ctx);
-    return RC_OK;
-}
-
-int rc_count_reads(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int min_count, int64_t *n_kmers)
-{
-    if (nbytes == 0 || nbytes >= (1ull << 32)) {
-        rc_set_error(ctx, "count: arena must be 1..2^32-1 bytes");
-        return RC_ERR_ARG;
-    }
-    int rc = rc_count_begin(ctx);
-    if (rc == RC_OK) rc = rc_count_add(ctx, d_seq, nbytes, true);
-    if (rc == RC_OK) rc = rc_count_finish(ctx, min_count, n_kmers);
-    return rc;
 }

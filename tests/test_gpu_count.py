@@ -171,6 +171,53 @@ def test_sharded_count_over_several_contexts_equals_one_gpus_count(rc, n_ctx, me
         c.close()
 
 
+def test_contexts_are_reusable_after_a_sharded_finish_that_kept_its_arenas(rc, monkeypatch):
+    """A sharded finish with rc_table_count_keep moves every context's arenas to its kept ones; the next count_begin must
+    give them up and start from nothing on every context.  A second sharded count on the same contexts, the pieces dealt
+    differently, with several slices per owner (RC_COUNT_MEM_MB=1: the owners' kept arrays append round after round), gives
+    the same table -- exact counts, digest, ERROR_RATE estimate -- as the first and as one context; and a recount session on
+    the first context (arenas of its own, beside the kept ones) sees every k-mer of the reads, the singletons as absent."""
+    k = 31
+    s1, _, _, _, _ = synth.make_reads(4200, 9000, 150, n_tx=6, l_tx=900, e=0.03)
+    want_k, want_c = synth.count_kmers([s1], k)
+    all_k, all_c = np.unique(synth.canonical_codes(s1, k), return_counts=True)
+    monkeypatch.setenv("RC_COUNT_MEM_MB", "1")
+    rows = [s1[i] for i in range(len(s1))]
+    pieces = [arena_of(rows[lo:lo + 1000]) for lo in range(0, len(rows), 1000)]
+    one = rc.Context(k=k)
+    one.count_begin()
+    for a in pieces:
+        one.count_add(a)
+    n_one = one.count_finish(2)
+    ctxs = [rc.Context(k=k) for _ in range(3)]
+    ctxs[0].count_keep(True)
+    seen = []
+    for deal in (lambda i: i % 3, lambda i: 0 if i < 5 else 1 + i % 2):   # evenly, then unevenly
+        for c in ctxs:
+            c.count_begin()
+            assert list(c.count_arenas()) == []
+        given = [[] for _ in ctxs]
+        for i, a in enumerate(pieces):
+            ctxs[deal(i)].count_add(a)
+            given[deal(i)].append(len(a))
+        n = ctxs[0].count_finish_sharded(ctxs[1:])
+        for c, want in zip(ctxs, given):
+            assert list(c.count_arenas()) == want
+        got_k, got_c = sorted_pairs(*ctxs[0].table_export())
+        assert n == n_one == len(want_k) and np.array_equal(got_k, want_k) and np.array_equal(got_c, want_c)
+        seen.append((ctxs[0].table_digest(), ctxs[0].estimate_error_rate(0.95)))
+    assert seen[0] == seen[1] == (one.table_digest(), one.estimate_error_rate(0.95))
+    ctxs[0].recount_begin()
+    for a in pieces:
+        ctxs[0].recount_add(a)
+    _, st = ctxs[0].recount_finish()
+    assert st["distinct"] == len(all_k) and st["total"] == int(all_c.sum())
+    assert st["absent_distinct"] == int((all_c == 1).sum()) > 0   # (the table holds the counts >= 2)
+    assert list(ctxs[0].count_arenas()) == given[0]               # (the session left the kept arenas alone)
+    for c in ctxs + [one]:
+        c.close()
+
+
 def test_count_sequence_errors(rc):
     ctx = rc.Context(k=23)
     with pytest.raises(rc.RcorrectorError):
