@@ -1,5 +1,5 @@
-// rc_api_batch.hip -- C ABI, the correction entry points (include/rcorrector_amd.h): HBM-resident batches, host batches
-// (synchronous, traced, per read) and the asynchronous host-buffer path (rc_submit / rc_wait slots).
+// rc_api_batch.hip -- C ABI, the correction entry points (include/rcorrector_amd.h): HBM-resident batches and host batches
+// (synchronous, traced, per read).  The asynchronous slot transports are rc_api_slots.hip's.
 #include "rc_api_internal.h"
 
 extern "C" {
@@ -282,16 +282,8 @@ int rc_correct_read(rc_ctx *ctx, char *seq, const char *qual, int32_t pair_stron
     ctx->cand_ready = false;
     if ((rc = rc_launch_correct(ctx, a))) return rc;
     if ((rc = rc_launch_summary(ctx, a.ret, 1))) return rc;
-    {
-        rc_device_batch db = rc_device_batch();
-        db.n_reads = 1;
-        db.nbytes = n1;
-        db.d_seq = a.seq;
-        db.d_qual = a.qual;
-        db.d_off = a.off;
-        db.d_ret = a.ret;
-        if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, 0, nullptr, nullptr))) return rc;
-    }
+    const rc_device_batch db = rc_device_batch_over(0, 1, n1, a.max_len, a.seq, a.qual, a.off, a.ret);  // (one_read_upload: a.ret | l | m | h is one block)
+    if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, 0, nullptr, nullptr))) return rc;
     RC_CHECK_HIP(ctx, hipMemcpyAsync(seq, a.seq, n1 - 1, hipMemcpyDeviceToHost, ctx->stream));
     RC_CHECK_HIP(ctx, hipMemcpyAsync(ret, a.ret, 4, hipMemcpyDeviceToHost, ctx->stream));
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -378,13 +370,7 @@ static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t)
         return RC_ERR_ARG;
     }
     std::vector<uint32_t> off(total_reads + 1);
-    int max_len = 0;
-    for (size_t i = 0; i <= n1; ++i) off[i] = b->off[i];
-    for (size_t i = 0; i < n1; ++i) max_len = std::max(max_len, (int)(b->off[i + 1] - b->off[i]) - 1);
-    if (b->mode == 1) {
-        for (size_t i = 0; i <= n1; ++i) off[n1 + i] = (uint32_t)bytes1 + b->off2[i];
-        for (size_t i = 0; i < n1; ++i) max_len = std::max(max_len, (int)(b->off2[i + 1] - b->off2[i]) - 1);
-    }
+    const int max_len = rc_concat_offsets(b, bytes1, off.data());
     int rc;
     if ((rc = rc_dbuf_reserve(ctx, &ctx->h_seq, nbytes + 64))) return rc;
     if ((rc = rc_dbuf_reserve(ctx, &ctx->h_qual, nbytes + 64))) return rc;
@@ -398,19 +384,7 @@ static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t)
         RC_CHECK_HIP(ctx, hipMemcpyAsync(d_qual + bytes1, b->qual2, bytes2, hipMemcpyHostToDevice, ctx->stream));
     }
     RC_CHECK_HIP(ctx, hipMemcpyAsync(ctx->h_off.p, off.data(), (total_reads + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    int32_t *d_res = (int32_t *)ctx->h_res.p;
-    rc_device_batch db;
-    db.mode = b->mode;
-    db.n_reads = (uint32_t)total_reads;
-    db.nbytes = nbytes;
-    db.max_read_len = max_len;
-    db.d_seq = d_seq;
-    db.d_qual = d_qual;
-    db.d_off = (const uint32_t *)ctx->h_off.p;
-    db.d_ret = d_res;
-    db.d_l = d_res + total_reads;
-    db.d_m = d_res + 2 * total_reads;
-    db.d_h = d_res + 3 * total_reads;
+    const rc_device_batch db = rc_device_batch_over(b->mode, total_reads, nbytes, max_len, d_seq, d_qual, (const uint32_t *)ctx->h_off.p, (int32_t *)ctx->h_res.p);
     if ((rc = rc_correct_device(ctx, &db))) return rc;
     RC_CHECK_HIP(ctx, hipMemcpyAsync(b->seq, d_seq, bytes1, hipMemcpyDeviceToHost, ctx->stream));
     if (b->mode == 1) RC_CHECK_HIP(ctx, hipMemcpyAsync(b->seq2, d_seq + bytes1, bytes2, hipMemcpyDeviceToHost, ctx->stream));
@@ -436,281 +410,6 @@ static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t)
     }
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return rc_recount_take(ctx, d_seq, nbytes);  // (rc_recount_follow: the traced entry point's batches complete here)
-}
-
-// ---- asynchronous host-buffer path ---------------------------------------------------------------
-// The reference overlaps the I/O of batch N+1 with the correction of batch N by handing batches to
-// worker threads (main.cpp:479-516).  Here one context keeps up to RC_MAX_SLOTS batches in flight on
-// three streams: H2D(N+1) || kernels(N) || D2H(N-1).  Scratch memory of the kernels is shared --
-// they serialise on the compute stream -- only the arenas and result arrays exist per slot.
-int rc_hbuf_reserve(rc_ctx *ctx, rc_hbuf *h, size_t bytes)
-{
-    if (bytes <= h->bytes) return RC_OK;
-    if (h->p) (void)hipHostFree(h->p);
-    h->p = nullptr;
-    h->bytes = 0;
-    const size_t want = bytes + bytes / 8 + 4096;
-    RC_CHECK_HIP(ctx, hipHostMalloc(&h->p, want, hipHostMallocDefault));
-    h->bytes = want;
-    return RC_OK;
-}
-
-static bool is_pinned_at(const void *p)
-{
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();  // pageable memory the runtime has never seen
-        return false;
-    }
-    return at.type == hipMemoryTypeHost;
-}
-
-// the whole range [p, p + bytes) is page-locked: its first and last byte are (a registration or a
-// hipHostMalloc block is one contiguous range, so a buffer that starts and ends inside pinned memory and was
-// handed over as one array lies in it -- unless it straddles two separate registrations, which then both
-// cover their part)
-bool rc_is_pinned(const void *p, size_t bytes)
-{
-    if (!p) return false;
-    if (!is_pinned_at(p)) return false;
-    return bytes <= 1 || is_pinned_at(static_cast<const char *>(p) + bytes - 1);
-}
-
-int rc_host_alloc(rc_ctx *ctx, size_t bytes, void **out)
-{
-    if (!ctx || !out) return RC_ERR_ARG;
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    RC_CHECK_HIP(ctx, hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault));
-    return RC_OK;
-}
-
-int rc_host_free(rc_ctx *ctx, void *p)
-{
-    if (!ctx) return RC_ERR_ARG;
-    if (p) RC_CHECK_HIP(ctx, hipHostFree(p));
-    return RC_OK;
-}
-
-// page-locks caller memory (any allocation, whole pages) so that rc_submit can DMA straight from / to it
-int rc_host_register(void *p, size_t bytes)
-{
-    if (!p || !bytes) return RC_ERR_ARG;
-    return hipHostRegister(p, bytes, hipHostRegisterPortable) == hipSuccess ? RC_OK : RC_ERR_HIP;
-}
-
-int rc_host_unregister(void *p)
-{
-    if (!p) return RC_ERR_ARG;
-    return hipHostUnregister(p) == hipSuccess ? RC_OK : RC_ERR_HIP;
-}
-
-int rc_slots_init(rc_ctx *ctx)
-{
-    if (ctx->slots) return RC_OK;
-    RC_CHECK_HIP(ctx, hipStreamCreateWithFlags(&ctx->s_h2d, hipStreamNonBlocking));
-    RC_CHECK_HIP(ctx, hipStreamCreateWithFlags(&ctx->s_d2h, hipStreamNonBlocking));
-    ctx->slots = new (std::nothrow) rc_slot[RC_MAX_SLOTS];
-    if (!ctx->slots) return RC_ERR_NOMEM;
-    for (int i = 0; i < RC_MAX_SLOTS; ++i) {
-        rc_slot &sl = ctx->slots[i];
-        RC_CHECK_HIP(ctx, hipEventCreateWithFlags(&sl.e_h2d, hipEventDisableTiming));
-        RC_CHECK_HIP(ctx, hipEventCreateWithFlags(&sl.e_k, hipEventDisableTiming));
-        RC_CHECK_HIP(ctx, hipEventCreateWithFlags(&sl.e_done, hipEventDisableTiming));
-    }
-    return RC_OK;
-}
-
-int rc_submit(rc_ctx *c, const rc_batch *b, int slot)
-{
-    if (!c || !b || slot < 0 || slot >= RC_MAX_SLOTS) return RC_ERR_ARG;
-    if (rc_ctx *ln = rc_slot_lane(c, slot, true, true); ln != c) {  // (slot lanes, rc_internal.h: this slot runs in a context of its own)
-        if (!ln) return RC_ERR_HIP;
-        const int lrc = rc_submit(ln, b, 0);
-        if (lrc) rc_lane_error(c, ln);
-        return lrc;
-    }
-    rc_ctx_full *ctx = static_cast<rc_ctx_full *>(c);
-    if (b->mode < 0 || b->mode > 2 || (b->n && (!b->seq || !b->qual || !b->off || !b->ret || !b->l || !b->m || !b->h)) ||
-        (b->n && b->mode == 1 && (!b->seq2 || !b->qual2 || !b->off2))) {
-        rc_set_error(ctx, "submit: bad batch descriptor");
-        return RC_ERR_ARG;
-    }
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = rc_slots_init(ctx);
-    if (rc) return rc;
-    rc_slot &sl = ctx->slots[slot];
-    if (sl.busy) {
-        rc_set_error(ctx, "submit: slot %d still holds a batch (rc_wait it first)", slot);
-        return RC_ERR_STATE;
-    }
-    sl.b = *b;
-    sl.pb = nullptr;
-    sl.rb = nullptr;
-    const size_t n1 = b->n;
-    sl.total_reads = b->mode == 1 ? 2 * n1 : n1;
-    sl.bytes1 = n1 ? b->off[n1] : 0;
-    sl.bytes2 = (n1 && b->mode == 1) ? b->off2[n1] : 0;
-    if (n1 == 0) {
-        sl.busy = true;
-        return RC_OK;
-    }
-    const size_t nbytes = sl.bytes1 + sl.bytes2, total = sl.total_reads;
-    sl.arena_bytes = nbytes;
-    if (nbytes >= (1ull << 32) || total >= (1ull << 32)) {
-        rc_set_error(ctx, "submit: batch too large (split it)");
-        return RC_ERR_ARG;
-    }
-    if (b->mode == 2 && (n1 & 1)) {  // (before any copy is queued)
-        rc_set_error(ctx, "submit: interleaved mode needs an even number of reads (got %zu)", n1);
-        return RC_ERR_ARG;
-    }
-    if (!ctx->d_buckets) {
-        rc_set_error(ctx, "correct: no k-mer table loaded");
-        return RC_ERR_STATE;
-    }
-    // offsets of the device arena (arena 1 then arena 2) and the longest read, into pinned memory
-    if ((rc = rc_hbuf_reserve(ctx, &sl.p_off, (total + 1) * 4))) return rc;
-    uint32_t *off = (uint32_t *)sl.p_off.p;
-    int max_len = 0;
-    memcpy(off, b->off, (n1 + 1) * 4);
-    for (size_t i = 0; i < n1; ++i) max_len = std::max(max_len, (int)(b->off[i + 1] - b->off[i]) - 1);
-    if (b->mode == 1) {
-        for (size_t i = 0; i <= n1; ++i) off[n1 + i] = (uint32_t)sl.bytes1 + b->off2[i];
-        for (size_t i = 0; i < n1; ++i) max_len = std::max(max_len, (int)(b->off2[i + 1] - b->off2[i]) - 1);
-    }
-    // quality arenas: a byte per base, or (rc_set_quality_bits) a bit per arena byte, arena 2's bits in
-    // a region of their own
-    const bool qbits = ctx->qual_bits;
-    const size_t q1 = qbits ? (sl.bytes1 + 7) / 8 : sl.bytes1, q2 = qbits ? (sl.bytes2 + 7) / 8 : sl.bytes2;
-    const size_t qbase2 = qbits ? ((q1 + 15) & ~(size_t)15) : sl.bytes1;
-    if ((rc = rc_dbuf_reserve(ctx, &sl.d_seq, nbytes + 64))) return rc;
-    if ((rc = rc_dbuf_reserve(ctx, &sl.d_qual, qbase2 + q2 + 64))) return rc;
-    if ((rc = rc_dbuf_reserve(ctx, &sl.d_off, (total + 1) * 4))) return rc;
-    if ((rc = rc_dbuf_reserve(ctx, &sl.d_res, total * 16))) return rc;
-    sl.seq_pinned = rc_is_pinned(b->seq, sl.bytes1) && rc_is_pinned(b->qual, q1) &&
-                    (b->mode != 1 || (rc_is_pinned(b->seq2, sl.bytes2) && rc_is_pinned(b->qual2, q2)));
-    sl.res_pinned = rc_is_pinned(b->ret, total * 4) && rc_is_pinned(b->l, total * 4) && rc_is_pinned(b->m, total * 4) && rc_is_pinned(b->h, total * 4);
-    const char *h_seq1 = b->seq, *h_qual1 = b->qual, *h_seq2 = b->seq2, *h_qual2 = b->qual2;
-    if (!sl.seq_pinned) {  // pageable buffers: through the slot's pinned staging
-        if ((rc = rc_hbuf_reserve(ctx, &sl.p_seq, nbytes))) return rc;
-        if ((rc = rc_hbuf_reserve(ctx, &sl.p_qual, qbase2 + q2))) return rc;
-        memcpy(sl.p_seq.p, b->seq, sl.bytes1);
-        memcpy(sl.p_qual.p, b->qual, q1);
-        if (b->mode == 1) {
-            memcpy((char *)sl.p_seq.p + sl.bytes1, b->seq2, sl.bytes2);
-            memcpy((char *)sl.p_qual.p + qbase2, b->qual2, q2);
-        }
-        h_seq1 = (const char *)sl.p_seq.p;
-        h_qual1 = (const char *)sl.p_qual.p;
-        h_seq2 = h_seq1 + sl.bytes1;
-        h_qual2 = h_qual1 + qbase2;
-    }
-    if (!sl.res_pinned && (rc = rc_hbuf_reserve(ctx, &sl.p_res, total * 16))) return rc;
-    uint8_t *d_seq = (uint8_t *)sl.d_seq.p, *d_qual = (uint8_t *)sl.d_qual.p;
-    // one upload stream: bases and qualities on two streams measured 21 GB/s against 26.6 GB/s on one
-    // (the link, not a DMA engine, is the bound)
-    hipStream_t sq = ctx->s_h2d;
-    // from here on copies are in flight from the caller's buffers (or the slot's staging): an error must not
-    // return before they have drained, or the caller could free / the next submit could overwrite memory the
-    // DMA engines still read
-    struct drain_on_error {
-        rc_ctx *c;
-        bool armed = true;
-        ~drain_on_error()
-        {
-            if (!armed) return;
-            (void)hipStreamSynchronize(c->s_h2d);
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipStreamSynchronize(c->s_d2h);
-        }
-    } guard{ctx};
-    RC_CHECK_HIP(ctx, hipMemcpyAsync(d_seq, h_seq1, sl.bytes1, hipMemcpyHostToDevice, ctx->s_h2d));
-    RC_CHECK_HIP(ctx, hipMemcpyAsync(d_qual, h_qual1, q1, hipMemcpyHostToDevice, sq));
-    if (b->mode == 1) {
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(d_seq + sl.bytes1, h_seq2, sl.bytes2, hipMemcpyHostToDevice, ctx->s_h2d));
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(d_qual + qbase2, h_qual2, q2, hipMemcpyHostToDevice, sq));
-    }
-    RC_CHECK_HIP(ctx, hipMemcpyAsync(sl.d_off.p, off, (total + 1) * 4, hipMemcpyHostToDevice, ctx->s_h2d));
-    RC_CHECK_HIP(ctx, hipEventRecord(sl.e_h2d, ctx->s_h2d));
-    // kernels
-    RC_CHECK_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.e_h2d, 0));
-    int32_t *d_res = (int32_t *)sl.d_res.p;
-    rc_device_batch db;
-    db.mode = b->mode;
-    db.n_reads = (uint32_t)total;
-    db.nbytes = nbytes;
-    db.max_read_len = max_len;
-    db.d_seq = d_seq;
-    db.d_qual = d_qual;
-    db.d_off = (const uint32_t *)sl.d_off.p;
-    db.d_ret = d_res;
-    db.d_l = d_res + total;
-    db.d_m = d_res + 2 * total;
-    db.d_h = d_res + 3 * total;
-    const uint32_t qsplit = qbits && b->mode == 1 ? (uint32_t)sl.bytes1 : 0xFFFFFFFFu;
-    if ((rc = rc_correct_device_impl(ctx, &db, qsplit, (uint32_t)qbase2))) return rc;
-    // (the correction report: no second submission on this path -- counted here, before the event rc_wait waits for)
-    if ((rc = rc_report_count(ctx, &db, qsplit, (uint32_t)qbase2, -1, nullptr, nullptr))) return rc;
-    RC_CHECK_HIP(ctx, hipEventRecord(sl.e_k, ctx->stream));
-    // results
-    RC_CHECK_HIP(ctx, hipStreamWaitEvent(ctx->s_d2h, sl.e_k, 0));
-    char *o_seq1 = sl.seq_pinned ? b->seq : (char *)sl.p_seq.p;
-    RC_CHECK_HIP(ctx, hipMemcpyAsync(o_seq1, d_seq, sl.bytes1, hipMemcpyDeviceToHost, ctx->s_d2h));
-    if (b->mode == 1) {
-        char *o_seq2 = sl.seq_pinned ? b->seq2 : (char *)sl.p_seq.p + sl.bytes1;
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(o_seq2, d_seq + sl.bytes1, sl.bytes2, hipMemcpyDeviceToHost, ctx->s_d2h));
-    }
-    if (sl.res_pinned) {
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(b->ret, db.d_ret, total * 4, hipMemcpyDeviceToHost, ctx->s_d2h));
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(b->l, db.d_l, total * 4, hipMemcpyDeviceToHost, ctx->s_d2h));
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(b->m, db.d_m, total * 4, hipMemcpyDeviceToHost, ctx->s_d2h));
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(b->h, db.d_h, total * 4, hipMemcpyDeviceToHost, ctx->s_d2h));
-    } else {
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(sl.p_res.p, d_res, total * 16, hipMemcpyDeviceToHost, ctx->s_d2h));
-    }
-    RC_CHECK_HIP(ctx, hipEventRecord(sl.e_done, ctx->s_d2h));
-    guard.armed = false;
-    sl.busy = true;
-    return RC_OK;
-}
-
-int rc_wait(rc_ctx *c, int slot)
-{
-    if (!c || slot < 0 || slot >= RC_MAX_SLOTS) return RC_ERR_ARG;
-    if (rc_ctx *ln = rc_slot_lane(c, slot, false, false); ln != c) {  // (slot lanes, rc_internal.h: this slot runs in a context of its own)
-        if (!ln) return RC_ERR_HIP;
-        const int lrc = rc_wait(ln, 0);
-        if (lrc) rc_lane_error(c, ln);
-        return lrc;
-    }
-    rc_ctx_full *ctx = static_cast<rc_ctx_full *>(c);
-    if (!ctx->slots || !ctx->slots[slot].busy) {
-        rc_set_error(ctx, "wait: slot %d holds no batch", slot);
-        return RC_ERR_STATE;
-    }
-    rc_slot &sl = ctx->slots[slot];
-    if (sl.pb || sl.rb) {
-        rc_set_error(ctx, "wait: slot %d holds a packed batch (rc_wait_packed / rc_wait_resident)", slot);
-        return RC_ERR_STATE;
-    }
-    sl.busy = false;
-    if (sl.b.n == 0) return RC_OK;
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    RC_CHECK_HIP(ctx, hipEventSynchronize(sl.e_done));
-    if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;  // (rc_recount_follow: before the slot can be reused)
-    const size_t total = sl.total_reads;
-    if (!sl.seq_pinned) {
-        memcpy(sl.b.seq, sl.p_seq.p, sl.bytes1);
-        if (sl.b.mode == 1) memcpy(sl.b.seq2, (char *)sl.p_seq.p + sl.bytes1, sl.bytes2);
-    }
-    if (!sl.res_pinned) {
-        const int32_t *r = (const int32_t *)sl.p_res.p;
-        memcpy(sl.b.ret, r, total * 4);
-        memcpy(sl.b.l, r + total, total * 4);
-        memcpy(sl.b.m, r + 2 * total, total * 4);
-        memcpy(sl.b.h, r + 3 * total, total * 4);
-    }
-    return RC_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // rc_api_internal.h -- what the translation units of the C ABI (rc_api*.hip) share: the context as the ABI layer sees it,
-// the slots of the asynchronous entry points, and the helpers that cross the units.
+// the slots of the asynchronous transports (rc_api_slots.hip), and the helpers that cross the units.
 #pragma once
 #include <algorithm>
 #include <cstdarg>
@@ -37,20 +37,36 @@ struct rc_hbuf {
     size_t bytes = 0;
 };
 
-// one batch in flight on the asynchronous host-buffer path
+// what a slot holds (rc_api_slots.hip): nothing -- it is free -- or a batch of one of the three transports, whose wait alone takes it
+enum rc_slot_kind { RC_SLOT_NONE, RC_SLOT_BYTES, RC_SLOT_PACKED, RC_SLOT_RESIDENT };
+
+// where a packed / resident batch's outputs go: the arrays of the caller's descriptor (valid until its wait) and its n_fix
+struct rc_slot_out {
+    int32_t *ret = nullptr, *l = nullptr, *m = nullptr, *h = nullptr;
+    uint32_t *fix_pos = nullptr;
+    uint8_t *fix_chr = nullptr;
+    size_t *n_fix = nullptr;
+};
+
+// one batch in flight on the asynchronous slot transports
 struct rc_slot {
-    bool busy = false;
-    rc_batch b;                      // the caller's descriptor (its buffers stay valid until rc_wait)
-    size_t total_reads = 0, bytes1 = 0, bytes2 = 0;
+    rc_slot_kind kind = RC_SLOT_NONE;
+    size_t total_reads = 0;          // reads of the batch over both arenas (0: an empty batch, nothing was queued)
     size_t arena_bytes = 0;          // bytes of the batch's arena in d_seq (what rc_recount_follow takes when the batch completes)
-    bool seq_pinned = false, res_pinned = false;  // the caller's buffers are page-locked: DMA straight from / to them
-    rc_hbuf p_seq, p_qual, p_off, p_res;           // pinned staging (seq/qual only when the caller's are pageable)
+    bool res_pinned = false;         // the caller's result arrays are page-locked: DMA straight to them, else through p_res
+    rc_hbuf p_res;
     rc_dbuf d_seq, d_qual, d_off, d_res;
     hipEvent_t e_h2d = nullptr, e_k = nullptr, e_done = nullptr;
-    // the packed boundary (rc_submit_packed): the caller's descriptor, the packed arena / exceptions / fix list in HBM,
-    // pinned staging for descriptor arrays that are not page-locked, and the fix count's landing place
-    rc_packed_batch *pb = nullptr;
-    rc_resident_batch *rb = nullptr;  // rc_submit_resident: same slot state, the arena copied from the counter's kept arenas
+    // the byte transport (rc_submit): the caller's descriptor (its buffers stay valid until rc_wait), the two arenas' sizes,
+    // and pinned staging for the offsets and for arenas that are pageable
+    rc_batch b;
+    size_t bytes1 = 0, bytes2 = 0;
+    bool seq_pinned = false;
+    rc_hbuf p_seq, p_qual, p_off;
+    // the packed and the resident transport: the outputs, the packed arena / exceptions / fix count in HBM (resident: the
+    // count only, its arena is copied from the counter's kept arenas), pinned staging for descriptor arrays that are not
+    // page-locked, and the fix count's landing place
+    rc_slot_out out;
     rc_dbuf d_packed, d_exc, d_fix;
     // correction report: a packed / resident batch's counts wait here until its wait accepts it (a batch that did not fit its
     // fix list comes again, and only then counts); rep_staged: this batch left some
@@ -61,15 +77,50 @@ struct rc_slot {
     bool fix_pinned = false;
 };
 
+// one rc_device_batch over a result block d_res = ret | l | m | h of `total` reads each
+static inline rc_device_batch rc_device_batch_over(int mode, size_t total, size_t nbytes, int max_len, uint8_t *d_seq, const uint8_t *d_qual,
+                                                   const uint32_t *d_off, int32_t *d_res)
+{
+    rc_device_batch db;
+    db.mode = mode;
+    db.n_reads = (uint32_t)total;
+    db.nbytes = nbytes;
+    db.max_read_len = max_len;
+    db.d_seq = d_seq;
+    db.d_qual = d_qual;
+    db.d_off = d_off;
+    db.d_ret = d_res;
+    db.d_l = d_res + total;
+    db.d_m = d_res + 2 * total;
+    db.d_h = d_res + 3 * total;
+    return db;
+}
+
+// the offsets of a host batch's device arena -- arena 1, then (mode 1) arena 2 behind arena 1's bytes1 bytes -- into off[total + 1];
+// returns the longest read, in bases
+static inline int rc_concat_offsets(const rc_batch *b, size_t bytes1, uint32_t *off)
+{
+    const size_t n1 = b->n;
+    int max_len = 0;
+    memcpy(off, b->off, (n1 + 1) * 4);
+    for (size_t i = 0; i < n1; ++i) max_len = std::max(max_len, (int)(b->off[i + 1] - b->off[i]) - 1);
+    if (b->mode == 1) {
+        for (size_t i = 0; i <= n1; ++i) off[n1 + i] = (uint32_t)bytes1 + b->off2[i];
+        for (size_t i = 0; i < n1; ++i) max_len = std::max(max_len, (int)(b->off2[i + 1] - b->off2[i]) - 1);
+    }
+    return max_len;
+}
 
 extern "C" {  // (defined inside the units' extern "C" blocks)
 // rc_api_batch.hip
 // qual_split / qual_base2 (quality-bit mode only): arena bytes from qual_split on have their bits at byte qual_base2 of d_qual;
 // qual_bits: -1 = as rc_set_quality_bits says, 0 / 1 = this batch's quality arena holds bytes / bits (the packed boundary)
 int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits = -1);
+// rc_api_slots.hip
 int rc_hbuf_reserve(rc_ctx *ctx, rc_hbuf *h, size_t bytes);
 bool rc_is_pinned(const void *p, size_t bytes);
 int rc_slots_init(rc_ctx *ctx);
+// rc_api.hip
 // the context slot `slot` runs in: ctx itself (slot 0, a lane, or RC_SLOT_LANES=0), else its lane -- created if `create`, and
 // brought up to date with ctx's table / parameters / kept arenas if `refresh` (submits); nullptr + error text on failure
 rc_ctx *rc_slot_lane(rc_ctx *ctx, int slot, bool create, bool refresh);

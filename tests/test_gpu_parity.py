@@ -866,6 +866,188 @@ def test_packed_boundary_slots_fasta_and_errors(gpu_ctx_factory, oracle):
     assert np.array_equal(ctx.wait_packed(0)[0], ret2)
 
 
+def _resident_inputs(ctx, oracle, d):
+    """d's reads counted and kept in HBM by ctx (a context without a table; the data set's own table and parameters go in
+    afterwards), and what a resident batch over all of them takes: the host arena (mode 1: first mates, then second mates), its
+    offsets, its quality bits in a page-locked array, and the range arguments."""
+    a, off = oracle.pack_reads(d["seqs1"])
+    qa, _ = oracle.pack_reads(d["quals1"])
+    ctx.count_keep(True)
+    ctx.count_begin()
+    ctx.count_add(a)
+    args = dict(arena_a=0, begin_a=0, bytes_a=a.size)
+    if d["mode"] == 1:
+        a2, off2 = oracle.pack_reads(d["seqs2"])
+        qa2, _ = oracle.pack_reads(d["quals2"])
+        ctx.count_add(a2)
+        args.update(arena_b=1, begin_b=0, bytes_b=a2.size)
+        off = np.concatenate([off, (off2[1:].astype(np.int64) + a.size).astype(np.uint32)])
+        a, qa = np.concatenate([a, a2]), np.concatenate([qa, qa2])
+    ctx.count_finish(2)
+    ctx.table_build(d["keys"], d["counts"])
+    ctx.set_run_params(d["rate"], b"H")
+    qb = ctx.host_array((a.size + 7) // 8)
+    ctx.pack_quality_bits(qa, b"H", out=qb)
+    return a, off, qb, args
+
+
+_PE_VAR_THIRDS = {}
+
+
+def _pe_var_third(oracle, j):
+    """(third j of pe_var as a data set of its own -- the cut of the slot tests above --, the oracle's results on it, the oracle's
+    corrected reads as one arena); the oracle runs once per third and nothing changes what it returned."""
+    if j not in _PE_VAR_THIRDS:
+        d = datasets.make("pe_var")
+        n1 = len(d["seqs1"])
+        lo, hi = j * n1 // 3, (j + 1) * n1 // 3
+        sub = dict(d, seqs1=d["seqs1"][lo:hi], quals1=d["quals1"][lo:hi], seqs2=d["seqs2"][lo:hi], quals2=d["quals2"][lo:hi])
+        want = datasets.run_oracle(oracle, sub)
+        _PE_VAR_THIRDS[j] = (sub, want, np.concatenate(want[4:]))
+    return _PE_VAR_THIRDS[j]
+
+
+def _fixes(before, after):
+    """the substitutions that turn arena `before` into `after`, as a fix list in ascending order"""
+    pos = np.nonzero(before != after)[0]
+    return list(zip(pos.tolist(), after[pos].tolist()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lanes", [True, False])
+def test_a_slot_knows_which_transports_batch_it_holds(gpu_ctx_factory, oracle, lanes):
+    """A byte batch, a packed batch and a resident batch in slots 0, 1 and 2 of one context: each slot refuses the waits of the
+    other two transports (RC_ERR_STATE, and says what it holds or does not hold), keeps its batch through that, and then gives
+    its own wait the oracle's ret / l / m / h and corrected bases -- with the slots above 0 in lanes of their own or not."""
+    RC_ERR_STATE = -4
+    subs = [_pe_var_third(oracle, j) for j in range(3)]
+    ctx = gpu_ctx_factory(subs[0][0]["k"], subs[0][0]["mfk"])
+    r_arena, r_off, r_qb, r_args = _resident_inputs(ctx, oracle, subs[2][0])   # (the three thirds share pe_var's table)
+    ctx.set_slot_lanes(lanes)
+    a1, o1 = oracle.pack_reads(subs[0][0]["seqs1"])
+    q1, _ = oracle.pack_reads(subs[0][0]["quals1"])
+    a2, o2 = oracle.pack_reads(subs[0][0]["seqs2"])
+    q2, _ = oracle.pack_reads(subs[0][0]["quals2"])
+    p_arena, p_off, bases, exc_pos, exc_chr, p_qb = _packed_inputs(ctx, oracle, subs[1][0])
+    ctx.submit(0, 1, a1, q1, o1, a2, q2, o2)
+    ctx.submit_packed(1, 1, p_arena.size, p_off, bases, p_qb, exc_pos, exc_chr)
+    ctx.submit_resident(2, 1, r_off, r_qb, **r_args)
+    L = ctx._L
+    wrong = {0: [(L.rc_wait_packed, "holds no packed batch"), (L.rc_wait_resident, "holds no resident batch")],
+             1: [(L.rc_wait, "holds a packed batch"), (L.rc_wait_resident, "holds no resident batch")],
+             2: [(L.rc_wait, "holds a packed batch"), (L.rc_wait_packed, "holds no packed batch")]}
+    for slot, calls in wrong.items():
+        for wait, text in calls:
+            rc = wait(ctx._h, slot)
+            assert rc == RC_ERR_STATE, "slot %d: rc = %d" % (slot, rc)
+            with pytest.raises(rcorrector_amd.RcorrectorError, match=text):   # (in a lane the text names the lane's own slot)
+                ctx._ck(rc)
+    got = [ctx.wait(0) + (np.concatenate([a1, a2]),)]
+    for wait, slot, arena in ((ctx.wait_packed, 1, p_arena), (ctx.wait_resident, 2, r_arena)):
+        ret, l, m, h, fix_pos, fix_chr = wait(slot)
+        host = arena.copy()
+        ctx.apply_fixes(host, fix_pos, fix_chr)
+        got.append((ret, l, m, h, host))
+    for slot, ((sub, want, want_arena), g) in enumerate(zip(subs, got)):
+        for w, x, what in zip(want[:4] + (want_arena,), g, ["ret", "l", "m", "h", "bases"]):
+            assert np.array_equal(w, x), "%s differs in slot %d" % (what, slot)
+    ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("transport", ["packed", "resident"])
+def test_packed_and_resident_results_land_wherever_the_caller_keeps_them(gpu_ctx_factory, oracle, transport):
+    """Where ret / l / m / h and the fix list go is the caller's choice: the binding's own arrays, four separate page-locked
+    arrays (a copy each), four consecutive views of one page-locked block (one copy of 16 bytes per read -- which must end where
+    the block's fourth array ends: the element behind it keeps its value), or pageable arrays (through the slot's staging, fix
+    list included).  The same batch every way: the oracle's ret / l / m / h and, as a set, the oracle's substitutions."""
+    sub, want, want_arena = _pe_var_third(oracle, 0)
+    if transport == "packed":
+        ctx = _table(gpu_ctx_factory, sub)
+        arena, off, bases, exc_pos, exc_chr, qb = _packed_inputs(ctx, oracle, sub)
+        submit, wait = (lambda **kw: ctx.submit_packed(0, 1, arena.size, off, bases, qb, exc_pos, exc_chr, **kw)), ctx.wait_packed
+    else:
+        ctx = gpu_ctx_factory(sub["k"], sub["mfk"])
+        arena, off, qb, args = _resident_inputs(ctx, oracle, sub)
+        submit, wait = (lambda **kw: ctx.submit_resident(0, 1, off, qb, **dict(args, **kw))), ctx.wait_resident
+    total, cap, GUARD = len(off) - 1, int(arena.size), -123456789
+    want_fixes = _fixes(np.asarray(arena), want_arena)
+    assert len(want_fixes) > 0
+    block = ctx.host_array(4 * total + 1, np.int32)
+    block[:] = GUARD
+    ways = {"defaults": {},
+            "four page-locked arrays": dict(res=[ctx.host_array(total, np.int32) for _ in range(4)], fix_pos=ctx.host_array(cap, np.uint32),
+                                            fix_chr=ctx.host_array(cap, np.uint8)),
+            "one page-locked block": dict(res=[block[i * total:(i + 1) * total] for i in range(4)], fix_pos=ctx.host_array(cap, np.uint32),
+                                          fix_chr=ctx.host_array(cap, np.uint8)),
+            "pageable arrays": dict(res=[np.full(total, GUARD, np.int32) for _ in range(4)], fix_pos=np.zeros(cap, np.uint32),
+                                    fix_chr=np.zeros(cap, np.uint8))}
+    for name, kw in ways.items():
+        submit(**kw)
+        ret, l, m, h, fix_pos, fix_chr = wait(0)
+        if "res" in kw:
+            assert all(g is r for g, r in zip((ret, l, m, h), kw["res"]))
+        for w, g, what in zip(want[:4], (ret, l, m, h), ["ret", "l", "m", "h"]):
+            assert np.array_equal(w, g), "%s differs with %s through the %s boundary" % (what, name, transport)
+        assert sorted(zip(fix_pos.tolist(), fix_chr.tolist())) == want_fixes, "the fix list differs with %s through the %s boundary" % (name, transport)
+    assert block[4 * total] == GUARD
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_resident_batch_without_room_for_its_fixes_frees_its_slot_and_counts_once(gpu_ctx_factory, oracle):
+    """rc_wait_resident on a batch whose fix list did not fit (fix_cap = 1) is an error that says so and leaves the slot free --
+    the batch is submitted again, with room, without a wait in between -- and only the resubmission counts: it gives the
+    oracle's results and substitutions, an armed correction report holds one submission's reads, and a recount session that
+    follows the context holds the k-mers of one corrected arena (test_recount's model of the oracle's reads)."""
+    from test_recount import canonical_codes
+    sub, want, want_arena = _pe_var_third(oracle, 0)
+    ctx = gpu_ctx_factory(sub["k"], sub["mfk"])
+    arena, off, qb, args = _resident_inputs(ctx, oracle, sub)
+    ctx.change_report_begin()
+    ctx.recount_begin()
+    ctx.recount_follow(True)
+    ctx.submit_resident(0, 1, off, qb, fix_cap=1, **args)
+    with pytest.raises(rcorrector_amd.RcorrectorError, match="room for 1"):
+        ctx.wait_resident(0)
+    ctx.submit_resident(0, 1, off, qb, **args)
+    ret, l, m, h, fix_pos, fix_chr = ctx.wait_resident(0)
+    for w, g, what in zip(want[:4], (ret, l, m, h), ["ret", "l", "m", "h"]):
+        assert np.array_equal(w, g), "%s differs on the resubmitted batch" % what
+    assert sorted(zip(fix_pos.tolist(), fix_chr.tolist())) == _fixes(arena, want_arena)
+    assert int(ctx.change_report()["reads"].sum()) == len(want[0])
+    ctx.change_report_end()
+    _freq, st = ctx.recount_finish()
+    assert st["total"] == sum(len(canonical_codes(a, sub["k"])) for a in want[4:]) > 0
+    ctx.close()
+
+
+@pytest.mark.gpu
+def test_empty_packed_and_resident_batches(gpu_ctx_factory, oracle):
+    """A batch of no reads through the packed and through the resident boundary: submit and wait succeed, there are no
+    results and no fixes, and the slot takes the next batch -- an empty one again, then one with reads, which gives the
+    oracle's results."""
+    sub, want, want_arena = _pe_var_third(oracle, 0)
+    ctx = gpu_ctx_factory(sub["k"], sub["mfk"])
+    arena, off, qb, args = _resident_inputs(ctx, oracle, sub)
+    _arena, _off, bases, exc_pos, exc_chr, p_qb = _packed_inputs(ctx, oracle, sub)
+    none32, none8, off0 = np.zeros(0, np.uint32), np.zeros(0, np.uint8), np.zeros(1, np.uint32)
+    for slot in (0, 1):
+        for _ in range(2):
+            ctx.submit_packed(slot, 1, 0, off0, none32, None, none32, none8)
+            desc = ctx._inflight_packed[slot][0]   # (the descriptor the library writes n_fix to)
+            assert [len(x) for x in ctx.wait_packed(slot)] == [0] * 6 and desc.n_fix == 0
+            ctx.submit_resident(slot, 1, off0, None, arena_a=0, begin_a=0, bytes_a=0)
+            desc = ctx._inflight_resident[slot][0]
+            assert [len(x) for x in ctx.wait_resident(slot)] == [0] * 6 and desc.n_fix == 0
+        ctx.submit_packed(slot, 1, arena.size, off, bases, p_qb, exc_pos, exc_chr)
+        assert np.array_equal(ctx.wait_packed(slot)[0], want[0])
+        ctx.submit_resident(slot, 1, off, qb, **args)
+        ret, l, m, h, fix_pos, fix_chr = ctx.wait_resident(slot)
+        assert np.array_equal(ret, want[0]) and sorted(zip(fix_pos.tolist(), fix_chr.tolist())) == _fixes(arena, want_arena)
+    ctx.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("lanes", [True, False])
 def test_slot_lanes_run_batches_side_by_side_with_the_same_results(gpu_ctx_factory, oracle, lanes):
