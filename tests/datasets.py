@@ -166,6 +166,39 @@ def make(name):
                 seqs1=r1, quals1=qq1, seqs2=r2, quals2=qq2)
 
 
+def revcomp_codes(codes, k):
+    """reverse complement of 2-bit k-mer codes (KmerCode.h:58-71), vectorised"""
+    out = np.zeros_like(codes)
+    c = codes.copy()
+    for _ in range(k):
+        out = (out << np.uint64(2)) | (np.uint64(3) - (c & np.uint64(3)))
+        c = c >> np.uint64(2)
+    return out
+
+
+def k_sweep(k, mode, pad_to=0):
+    """The k sweep's data set (tests/test_k_sweep.py): 600 reads (mode 1: pairs) of 100 bases over six transcripts of 400,
+    1 % substitutions, the exact counts of their own k-mers as the table.  With pad_to > 0 the table is padded to that many
+    entries with canonical k-mers that no read holds (counts 2..199), so that it has the size -- and so the layout and the
+    compiled-for-k kernel instance -- of a real one; the oracle gets the same padded table."""
+    s1, q1, s2, q2, _ = synth.make_reads(7100 + k, 600, 100, n_tx=6, l_tx=400, e=0.01, paired=mode == 1)
+    keys, cnt = synth.count_kmers([s1, s2], k)
+    if pad_to > len(keys):
+        rng = np.random.Generator(np.random.PCG64(9100 + k))
+        mask = np.uint64((1 << (2 * k)) - 1) if k < 32 else np.uint64(0xFFFFFFFFFFFFFFFF)
+        fwd = rng.integers(0, 1 << 63, size=pad_to + pad_to // 8, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=pad_to + pad_to // 8, dtype=np.uint64)
+        fwd &= mask
+        pad = np.unique(np.minimum(fwd, revcomp_codes(fwd, k)))
+        pad = rng.permutation(pad[~np.isin(pad, keys)])[:pad_to - len(keys)]
+        assert len(keys) + len(pad) == pad_to, "k = %d has too few k-mers to pad a table to %d entries" % (k, pad_to)
+        keys = np.concatenate([keys, pad])
+        cnt = np.concatenate([cnt, rng.integers(2, 200, size=len(pad)).astype(np.int64)])
+
+    def rows(a):
+        return None if a is None else [r.tobytes() for r in a]
+    return dict(k=k, mfk=4, rate=0.01, mode=mode, keys=keys, counts=cnt, seqs1=rows(s1), quals1=rows(q1), seqs2=rows(s2), quals2=rows(q2))
+
+
 def run_oracle(po, d, threads=4, fn=None):
     """Runs the oracle (or any same-signature batch function) on data set d.
     Returns (ret, l, m, h, corrected_arena1[, corrected_arena2])."""
