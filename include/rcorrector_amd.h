@@ -230,6 +230,44 @@ int rc_change_report_begin(rc_ctx *ctx);
 int rc_change_report_get(rc_ctx *ctx, rc_change_report *out);
 int rc_change_report_end(rc_ctx *ctx);
 
+/* ---- per-read weak-k-mer profile: which reads are still bad, and at which end ----------------------------------------------
+ * For one read of L bases, at the context's k, against the context's table, with a threshold min_count >= 1: window i
+ * (0 <= i <= L - k; none if L < k) is VALID if its k bytes are all upper-case ACGT exactly as the kernels read letters (lower
+ * case, N and anything else make it invalid), a valid window is SOLID if GetCount of its canonical k-mer (Store.h:59-66) is at
+ * least min_count and WEAK otherwise; invalid windows are neither.
+ *   weak        number of weak windows
+ *   bad_prefix  start of the first solid window
+ *   bad_suffix  L - (start of the last solid window + k)
+ *   uncovered   L - the number of bases that lie in at least one solid window (gaps in the middle count)
+ * A read without a solid window has bad_prefix = bad_suffix = uncovered = L; L = 0 gives four zeros.  So bad_prefix +
+ * bad_suffix <= uncovered <= L where a solid window exists, and with min_count = 1 the sum of `weak` over an arena is
+ * rc_recount_stats.absent_total of a recount of the same arena.  Nothing is trimmed, dropped or reordered: the numbers only
+ * annotate.  No reference counterpart: the reference carries the fields (_Read::badPrefix / badSuffix, Reads.h:20) and the
+ * output branch that prints them (Reads.h:396-412) but hard-wires both to 0 (Reads.h:371-372). */
+typedef struct { int32_t weak, bad_prefix, bad_suffix, uncovered; } rc_read_weak;   /* 16 bytes per read */
+/* The reads of an arena in HBM as they are (call it behind rc_correct_device for the corrected ones): d_out[r] for each of the
+ * n_reads reads (read r the NUL-terminated string at d_off[r]; d_off has n_reads + 1 entries).  Asynchronous on the context's
+ * stream, like rc_strong_threshold_device (rc_sync() to wait).  Needs a table; d_seq is never written, and may be read in
+ * aligned 16-byte pieces up to 15 bytes in front of its first and behind its last byte, as the correction report does.
+ * max_read_len is not used: the reduce takes one read per lane, which walks the plane words of a read of any length (reads
+ * of very different lengths in one wavefront wait for its longest).  RC_STATUS_ARG: min_count < 1, a null pointer with
+ * n_reads > 0; RC_STATUS_STATE: no table.  rc_profile_get's kernel 4 times it.
+ * No reference counterpart: the dormant fields of Reads.h:20,371-372,396-412. */
+int rc_weak_profile_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_off, uint32_t n_reads, uint64_t nbytes,
+                           int32_t max_read_len, int32_t min_count, rc_read_weak *d_out);
+/* One-shot: the NEXT batch submitted into `slot` (rc_submit / rc_submit_packed / rc_submit_resident, slots that run in lanes
+ * included; rc_correct_batch is slot 0) also profiles its corrected reads, on the GPU behind its last correction kernel;
+ * out[total] (indexed like ret / l / m / h) holds them when that batch's wait returns success.  The submit consumes the
+ * registration whether it succeeds or not: a batch resubmitted after RC_STATUS_NOSPACE registers again.  out == NULL
+ * withdraws (min_count is not looked at then).  A page-locked `out` (rc_host_alloc) is written by DMA, any other through the
+ * slot's staging by the wait that succeeds: where the wait fails (RC_STATUS_NOSPACE), a page-locked `out` may already have
+ * been written and its content means nothing, any other is untouched.  Without a
+ * registration a submit launches, copies and allocates nothing for it, and with or without one the corrected reads, ret / l /
+ * m / h, rc_summary and rc_table_digest are the same.  rc_correct_batch_traced takes no slot: it ignores a registration and
+ * leaves it for the next submit.  RC_STATUS_ARG: min_count < 1, a bad slot; RC_STATUS_STATE: no table.
+ * No reference counterpart: the dormant fields of Reads.h:20,371-372,396-412. */
+int rc_weak_profile_into(rc_ctx *ctx, int slot, rc_read_weak *out, int32_t min_count);
+
 /* ---- run parameters (globals of main.cpp:17-30) ----------------------------------------------- */
 /* replaces main.cpp:310-358 (ERROR_RATE estimation).  Uses the entries parsed by the last
  * rc_table_load_jfdump() in file order -- or, for a table that was counted here or built from
@@ -458,7 +496,7 @@ int rc_profile_correct_counters(rc_ctx *ctx, uint64_t *reads_listed, uint64_t *g
  * reads finished before that kernel are not written) -- which reads of a batch the search works hardest on
  * (MAX_TRIAL, ErrorCorrection.cpp:7; the straggler of tools/find_straggler.py).  NULL switches it off. */
 int rc_profile_read_rounds(rc_ctx *ctx, int32_t *d_rounds);
-/* kernel 0 = probe, 1 = threshold, 2 = correct; accumulated since the last reset */
+/* kernel 0 = probe, 1 = threshold, 2 = correct, 3 = isolated substitutions, 4 = weak-k-mer profile; accumulated since the last reset */
 int rc_profile_get(rc_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
 int rc_profile_reset(rc_ctx *ctx);
 

@@ -18,6 +18,7 @@ ABI_SYMBOLS = [
     "rc_table_count_spectrum", "rc_table_spectrum",
     "rc_recount_begin", "rc_recount_add", "rc_recount_add_device", "rc_recount_follow", "rc_recount_finish",
     "rc_change_report_begin", "rc_change_report_get", "rc_change_report_end",
+    "rc_weak_profile_device", "rc_weak_profile_into",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
@@ -85,6 +86,11 @@ class _ChangeReport(C.Structure):
     _fields_ = [("reads", C.c_uint64 * 2), ("reads_changed", C.c_uint64 * 2), ("reads_unfixable", C.c_uint64 * 2), ("changes", C.c_uint64 * 2),
                 ("len_hist", C.c_uint64 * REPORT_MAX_LEN * 2), ("by_pos5", C.c_uint64 * REPORT_MAX_LEN * 2), ("by_pos3", C.c_uint64 * REPORT_MAX_LEN * 2),
                 ("subst", C.c_uint64 * 4 * 5), ("by_qual", C.c_uint64 * 3), ("per_read", C.c_uint64 * (REPORT_MAX_PER_READ + 1))]
+
+
+class _ReadWeak(C.Structure):
+    """rc_read_weak: 16 bytes per read"""
+    _fields_ = [("weak", C.c_int32), ("bad_prefix", C.c_int32), ("bad_suffix", C.c_int32), ("uncovered", C.c_int32)]
 
 
 class _DeviceBatch(C.Structure):
@@ -162,6 +168,8 @@ def load_library():
     L.rc_change_report_begin.argtypes = [vp]
     L.rc_change_report_get.argtypes = [vp, C.POINTER(_ChangeReport)]
     L.rc_change_report_end.argtypes = [vp]
+    L.rc_weak_profile_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, vp]
+    L.rc_weak_profile_into.argtypes = [vp, C.c_int, vp, C.c_int32]
     L.rc_estimate_error_rate.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.rc_bad_quality_from_hist.restype = C.c_char
     L.rc_bad_quality_from_hist.argtypes = [vp, vp, C.c_int32]
@@ -426,6 +434,32 @@ class Context:
     def change_report_end(self):
         """rc_change_report_end: disarms the report and frees what it held."""
         self._ck(self._L.rc_change_report_end(self._h))
+
+    # ---- per-read weak-k-mer profile: weak windows, bad prefix / suffix, uncovered bases ----
+    def weak_profile_device(self, d_seq, d_off, n_reads, nbytes, max_read_len, d_out, min_count=1):
+        """rc_weak_profile_device: the reads of an arena in HBM as they are; d_out: device memory for n_reads x 4 int32
+        (weak, bad_prefix, bad_suffix, uncovered: rc_read_weak).  Asynchronous: sync() to wait."""
+        self._ck(self._L.rc_weak_profile_device(self._h, _ptr(d_seq), _ptr(d_off), n_reads, nbytes, max_read_len, int(min_count), _ptr(d_out)))
+
+    def weak_profile_into(self, slot, total_reads, min_count=1, out=None):
+        """rc_weak_profile_into: the next batch submitted into `slot` (correct_batch: slot 0) also profiles its corrected reads.
+        Returns a page-locked (total_reads, 4) int32 array -- columns weak, bad_prefix, bad_suffix, uncovered, rows indexed like
+        ret / l / m / h -- that the batch's wait fills (out: a C-contiguous int32 array of that shape to fill instead, e.g. a
+        pageable one).  One shot: every submit consumes the registration."""
+        total_reads = int(total_reads)
+        if out is None:
+            out = self.host_array(total_reads * 4, dtype=np.int32).reshape(total_reads, 4)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.shape == (total_reads, 4)):
+            raise TypeError("out must be a C-contiguous int32 numpy array of shape (total_reads, 4)")
+        self._ck(self._L.rc_weak_profile_into(self._h, int(slot), out.ctypes.data, int(min_count)))
+        if not hasattr(self, "_weak_out"):
+            self._weak_out = {}
+        self._weak_out[int(slot)] = out   # (the library writes it until the batch's wait returns)
+        return out
+
+    def weak_profile_withdraw(self, slot):
+        """rc_weak_profile_into(out = NULL): the next batch of `slot` is not profiled after all"""
+        self._ck(self._L.rc_weak_profile_into(self._h, int(slot), None, 1))
 
     # ---- run parameters ----
     def estimate_error_rate(self, wk=0.95):

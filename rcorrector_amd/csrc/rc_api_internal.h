@@ -73,6 +73,12 @@ struct rc_slot {
     rc_dbuf d_rep;
     bool rep_staged = false;
     rc_hbuf p_in, p_fix, p_nfix;
+    // weak-k-mer profile of the batch in flight (rc_weak_profile_into): the caller's array (nullptr: none asked for), the 16
+    // bytes per read in HBM, and their staging where the caller's array is not page-locked
+    void *weak_out = nullptr;
+    bool weak_pinned = false;
+    rc_dbuf d_weak;
+    rc_hbuf p_weak;
     uint32_t fix_room = 0;
     bool fix_pinned = false;
 };

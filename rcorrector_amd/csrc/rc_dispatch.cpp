@@ -291,6 +291,15 @@ static void format_job(Run &R, Job &J)
     for (auto &v : o1) v.clear();
     for (auto &v : o2) v.clear();
     std::vector<uint64_t> cor(S, 0);  // (the writer thread is the pipeline's narrow place: it only writes)
+    const rc_read_weak *wk = R.weak_ends ? J.weak.data() : nullptr;  // -weak-ends: the tags, and the reads that have them
+    const size_t WS = wk ? S : 0;
+    std::vector<uint64_t> wpre(WS, 0), wsuf(WS, 0), wnone(WS, 0);
+    auto tally = [&](size_t s, const Arena &A, size_t r, size_t gi) {
+        const int32_t L = (int32_t)(A.off[r + 1] - A.off[r]) - 1;
+        wpre[s] += wk[gi].bad_prefix > 0;
+        wsuf[s] += wk[gi].bad_suffix > 0;
+        wnone[s] += L > 0 && wk[gi].uncovered == L;
+    };
     auto fmt = [&](size_t lo, size_t hi) {
         for (size_t s = lo; s < hi; ++s) {
             const size_t r0 = n * s / S, r1 = n * (s + 1) / S;
@@ -298,23 +307,33 @@ static void format_job(Run &R, Job &J)
             for (size_t r = r0; r < r1; ++r) {
                 if (j->ret[r] > 0) c += (uint64_t)j->ret[r];
                 if (j->mode == 1 && j->ret[n + r] > 0) c += (uint64_t)j->ret[n + r];
+                if (wk) {
+                    tally(s, j->a, r, r);
+                    if (j->mode == 1) tally(s, j->b, r, n + r);
+                }
             }
             cor[s] = c;
             o1[s].reserve((r1 - r0) * 300);
             for (size_t r = r0; r < r1; ++r) {
-                put_record(o1[s], j->a, r, j->fastq, j->ret[r], j->l[r], j->m[r], j->h[r]);
-                if (alternate) put_record(o1[s], j->b, r, j->fastq, j->ret[n + r], j->l[n + r], j->m[n + r], j->h[n + r]);
+                put_record(o1[s], j->a, r, j->fastq, j->ret[r], j->l[r], j->m[r], j->h[r], wk ? wk + r : nullptr);
+                if (alternate) put_record(o1[s], j->b, r, j->fastq, j->ret[n + r], j->l[n + r], j->m[n + r], j->h[n + r], wk ? wk + n + r : nullptr);
             }
             if (j->mode == 1 && !alternate) {
                 o2[s].reserve((r1 - r0) * 300);
                 for (size_t r = r0; r < r1; ++r)
-                    put_record(o2[s], j->b, r, j->fastq, j->ret[n + r], j->l[n + r], j->m[n + r], j->h[n + r]);
+                    put_record(o2[s], j->b, r, j->fastq, j->ret[n + r], j->l[n + r], j->m[n + r], j->h[n + r], wk ? wk + n + r : nullptr);
             }
         }
     };
     g_pool.run(S, [&](size_t s) { fmt(s, s + 1); });
     J.cor_bases = 0;
     for (uint64_t c : cor) J.cor_bases += c;
+    J.weak_prefix = J.weak_suffix = J.weak_nosolid = 0;
+    for (size_t s = 0; s < WS; ++s) {
+        J.weak_prefix += wpre[s];
+        J.weak_suffix += wsuf[s];
+        J.weak_nosolid += wnone[s];
+    }
     if (gz1 || gz2) {  // deflate every slice into its own gzip member, in parallel
         std::vector<OutBuf> z1(S), z2(S);
         g_pool.run(S, [&](size_t s) {
@@ -403,6 +422,10 @@ static void worker_body(Run &R, int wk)
         j->l.assign(total, 0);
         j->m.assign(total, 0);
         j->h.assign(total, 0);
+        // -weak-ends: the batch about to be submitted into this worker's slot also profiles its corrected reads (one shot: a batch
+        // that is submitted again registers again); called with the GPU's submit lock held, in front of the submit
+        if (R.weak_ends) j->weak.assign(total, rc_read_weak());
+        auto arm_weak = [&]() { return R.weak_ends ? rc_weak_profile_into(ctx[g], slot, j->weak.data(), R.weak_min) : 0; };
         bool resident_done = false;
         int rrc = 0;
         double tq1 = tp0;
@@ -449,7 +472,7 @@ static void worker_body(Run &R, int wk)
                 rb.fix_cap = cap;
                 {
                     std::lock_guard<std::mutex> lk(submit_mu[(size_t)g]);
-                    rrc = rc_submit_resident(ctx[g], &rb, slot);
+                    if (!(rrc = arm_weak())) rrc = rc_submit_resident(ctx[g], &rb, slot);
                 }
                 if (!rrc) rrc = rc_wait_resident(ctx[g], slot);
                 // more substitutions than the list has room for (a heavily corrected tail batch: the list is sized for one fix
@@ -607,13 +630,13 @@ static void worker_body(Run &R, int wk)
             pb.fix_cap = cap;
             {
                 std::lock_guard<std::mutex> lk(submit_mu[(size_t)g]);
-                rc = rc_submit_packed(ctx[g], &pb, slot);
+                if (!(rc = arm_weak())) rc = rc_submit_packed(ctx[g], &pb, slot);
             }
             if (!rc) rc = rc_wait_packed(ctx[g], slot);
             if (rc == RC_STATUS_NOSPACE) {  // (see the resident path) the arenas are untouched: once more, as bytes
                 {
                     std::lock_guard<std::mutex> lk(submit_mu[(size_t)g]);
-                    rc = rc_submit(ctx[g], &rb, slot);
+                    if (!(rc = arm_weak())) rc = rc_submit(ctx[g], &rb, slot);
                 }
                 if (!rc) rc = rc_wait(ctx[g], slot);
                 pb.n_fix = 0;
@@ -634,7 +657,7 @@ static void worker_body(Run &R, int wk)
             {   // upload + kernels + download are queued here; the wait below overlaps with the other
                 // workers' packing, submitting and formatting
                 std::lock_guard<std::mutex> lk(submit_mu[(size_t)g]);
-                rc = rc_submit(ctx[g], &rb, slot);
+                if (!(rc = arm_weak())) rc = rc_submit(ctx[g], &rb, slot);
             }
             if (!rc) rc = rc_wait(ctx[g], slot);
         }
@@ -736,6 +759,9 @@ for (;;) {
     }
     total_reads += j->ret.size();  // UpdateSummary, main.cpp:73-79
     total_cor += j->cor_bases;
+    R.weak_prefix += j->weak_prefix;
+    R.weak_suffix += j->weak_suffix;
+    R.weak_nosolid += j->weak_nosolid;
     bool retire = false;
     {
         std::lock_guard<std::mutex> lk(mu);

@@ -32,6 +32,11 @@ struct Run {
     bool resident = false;  // one pass: the batches are `kept`, their bases in HBM
     bool numa_on = true, shared_gpu = false;
     char bad_q = 0;
+    // -weak-ends: every batch also asks for its corrected reads' weak-k-mer profile (rc_weak_profile_into, k-mers counted below
+    // weak_min are weak), the records carry the reference's bad_prefix / bad_suffix tags, and the writer adds up three counts
+    bool weak_ends = false;
+    int weak_min = 1;
+    uint64_t weak_prefix = 0, weak_suffix = 0, weak_nosolid = 0;
     bool recount_host = false;  // -histo-after with several GPUs: the workers hand every corrected batch's bases to ctx[0]'s recount session
     std::vector<ReadFile> files, mates;
     std::vector<rc_ctx *> ctx;                // one per GPU (the table is replicated)

@@ -1,6 +1,7 @@
 // rc_format.h -- a batch between the reader and the writer of the `rcorrector` CLI: the SoA arenas of the C ABI packed from
 // the text, quality bits and fixes of the one-pass path, and the output records.
 //   record       Reads.h:224-266,360-421    4 lines in; "<id> l:%d m:%d h:%d[ cor| unfixable_error]" out
+//   -weak-ends   Reads.h:396-412            " bad_prefix=%d" / " bad_suffix=%d" behind " cor": the reference's dormant tags
 //   transcript   ErrorCorrection.cpp:686-689,759-770,856-857,1088-1094,1590-1597 (-verbose)
 #pragma once
 #include <emmintrin.h>
@@ -33,6 +34,8 @@ struct Job {
     Arena a, b;
     std::vector<int32_t> ret, l, m, h;
     std::vector<int32_t> tr_before, tr_after, tr_flags, tr_niter, tr_iter;  // -verbose only
+    std::vector<rc_read_weak> weak;  // -weak-ends only: the corrected reads' profile, indexed like ret (rc_weak_profile_into)
+    uint64_t weak_prefix = 0, weak_suffix = 0, weak_nosolid = 0;  // ... and the reads with a bad prefix / a bad suffix / no solid k-mer
     bool resident = false;        // the batch's reads are arenas the k-mer counter kept in HBM (rc_submit_resident)
     int arena_a = 0, arena_b = 0;
     int gpu = -1;                 // the GPU that holds them (-1: any GPU may take the batch)
@@ -102,15 +105,17 @@ static inline char *put_int(char *p, int v)
 
 // Reads.h:360-421: one record.  The quality line is printed as fgets left it in the reference:
 // stripped of its newline only when it is exactly as long as the sequence line (Reads.h:255-262).
+// wk (-weak-ends): the read's weak-k-mer profile -- the tags of the reference's dormant branch (Reads.h:396-412) follow " cor",
+// each only where its value is above 0; the unfixable branch (:389) has none.  nullptr: the record as without the flag.
 template <class B>
-static inline void put_record(B &out, const Arena &A, size_t r, bool fastq, int cor, int l, int m, int h)
+static inline void put_record(B &out, const Arena &A, size_t r, bool fastq, int cor, int l, int m, int h, const rc_read_weak *wk = nullptr)
 {
     uint32_t il, ql = 0;
     const char *id = A.line(r, 0, &il);
     const char *seq = A.sequence(r);
     const uint32_t sl = A.off[r + 1] - A.off[r] - 1;
     const char *q = fastq ? A.line(r, 3, &ql) : nullptr;
-    const size_t need = (size_t)il + sl + ql + 96;
+    const size_t need = (size_t)il + sl + ql + 96 + (wk ? 48 : 0);
     const size_t at = out.size();
     out.resize(at + need);
     char *p = out.data() + at;
@@ -128,6 +133,16 @@ static inline void put_record(B &out, const Arena &A, size_t r, bool fastq, int 
     } else if (cor > 0) {
         memcpy(p, " cor", 4);
         p += 4;
+    }
+    if (wk && cor != -1) {
+        if (wk->bad_prefix > 0) {
+            memcpy(p, " bad_prefix=", 12);
+            p = put_int(p + 12, wk->bad_prefix);
+        }
+        if (wk->bad_suffix > 0) {
+            memcpy(p, " bad_suffix=", 12);
+            p = put_int(p + 12, wk->bad_suffix);
+        }
     }
     *p++ = '\n';
     memcpy(p, seq, sl);

@@ -73,7 +73,7 @@ struct rc_kernel_timer {
     uint64_t launches = 0;
 };
 
-enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_COUNT };
+enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_COUNT };
 
 struct rc_ctx {
     int device = 0;
@@ -153,6 +153,17 @@ struct rc_ctx {
     unsigned long long *rep_acc = nullptr;
     rc_dbuf rep_snap;
     const uint8_t *rep_snap_cur = nullptr;
+    // weak-k-mer profile (rc_weak_profile_device / rc_weak_profile_into; kernels in rc_weak.hip).  weak_planes: the two bit planes
+    // of the arena profiled last, scratch of the context the kernels run in (they serialise on its compute stream).  weak_reg:
+    // per slot of THIS context's entry points, where the next batch submitted there leaves its reads' profile (out == nullptr:
+    // nowhere) -- the submit takes it and hands it to the context the batch runs in (a lane included) as weak_cur, which the
+    // slot's download step consumes
+    struct rc_weak_reg {
+        void *out = nullptr;  // rc_read_weak[total]
+        int32_t min_count = 1;
+    };
+    rc_dbuf weak_planes;
+    rc_weak_reg weak_reg[4], weak_cur;
 
     // batch scratch
     rc_dbuf counts;   // int32 per arena byte
@@ -282,6 +293,10 @@ int rc_launch_kmer_info(rc_ctx *ctx, const rc_device_batch_args &a);
 // every read of the batch against d_snap (the arena before correction, at the arena's alignment modulo 16), counted into d_out
 int rc_launch_change_report(rc_ctx *ctx, const rc_device_batch_args &a, const uint8_t *d_snap, unsigned long long *d_out);
 int rc_launch_report_commit(rc_ctx *ctx, const unsigned long long *d_staged, unsigned long long *d_out);
+
+// rc_weak.hip: solid / weak bit planes of the arena into `planes` (grow-only), then d_out[r] = the rc_read_weak of read r
+int rc_launch_weak_profile(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int min_count, rc_dbuf *planes,
+                           void *d_out);
 
 // rc_transport.hip: the packed boundary (include/rcorrector_amd.h: rc_packed_batch)
 int rc_launch_unpack(rc_ctx *ctx, const uint32_t *d_packed, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, const uint32_t *d_exc_pos,

@@ -25,6 +25,8 @@
 // rc_recount_begin) and adds one line to stderr: how many of their k-mers the table does not hold.
 // -report FILE writes the correction report (rcorrector_amd.h: rc_change_report; rc_format.h: write_change_report): the
 // substitutions by position, letters, quality class, mate and read, counted on the GPU as the batches complete.
+// -weak-ends tags every record with the reference's dormant bad_prefix= / bad_suffix= fields (Reads.h:396-412), filled from the
+// weak-k-mer profile of the corrected reads (rcorrector_amd.h: rc_read_weak; -weak-min: the count below which a k-mer is weak).
 #include <fcntl.h>
 #include <malloc.h>
 #include <sys/stat.h>
@@ -68,6 +70,11 @@ static void print_help()
             "\t-report STRING: also write the correction report, tab-separated text: reads, changed bases by position from either end,\n"
             "\t\tby substitution, by quality class and per read, for each mate; counted on the GPU as the batches complete; with -gpus\n"
             "\t\tabove 1 every GPU keeps a report of its own and the file holds their sum\n"
+            "\t-weak-ends: tag every record, behind l:m:h and cor, with bad_prefix=N / bad_suffix=N where N > 0: the bases of the corrected\n"
+            "\t\tread in front of its first / behind its last k-mer that the table holds (unfixable reads keep their mark and get no tag);\n"
+            "\t\tnothing is trimmed; one more line on stderr counts the reads with a bad prefix, a bad suffix, and no such k-mer at all\n"
+            "\t\t(every read counts there, unfixable ones included); not with -verbose\n"
+            "\t-weak-min INT: with -weak-ends, a k-mer counted fewer times than this in the table is weak (default: 1)\n"
             "\t-verbose-iter INT: threshold iterations recorded per read for -verbose (default: 64)\n");
 }
 
@@ -138,6 +145,10 @@ int main(int argc, char **argv)
             histo_after = argv[++i];
         else if (!strcmp("-report", argv[i]))
             report = argv[++i];
+        else if (!strcmp("-weak-ends", argv[i]))
+            run.weak_ends = true;
+        else if (!strcmp("-weak-min", argv[i]))
+            run.weak_min = atoi(argv[++i]);
         else if (!strcmp("-packed", argv[i]))
             g_packed = true;
         else if (!strcmp("-h", argv[i])) {
@@ -149,6 +160,8 @@ int main(int argc, char **argv)
         }
     }
     g_verbose = verbose;
+    if (run.weak_ends && verbose) die("rcorrector: usage: -weak-ends cannot be combined with -verbose (the transcript's entry point takes no weak-k-mer profile)\n");
+    if (run.weak_min < 1) die("rcorrector: usage: -weak-min must be at least 1\n");
     if (g_trace_iter < 1) g_trace_iter = 1;
     // -verbose carries RC_TRACE_ITER_WORDS x trace-iter words per read through host and device
     // (9 KB per read at the default 64 iterations): small batches, or a real data set needs tens of GB
@@ -520,6 +533,9 @@ int main(int argc, char **argv)
     if (g_timing)
         fprintf(stderr, "[rc timing] blocked: reader %.2f s (no free slot), workers %.2f s (no batch), writer %.2f s (next batch not done)\n", g_w_reader, g_w_worker, g_w_writer);
     fprintf(stderr, "Processed %llu reads\n\tCorrected %llu bases.\n", (unsigned long long)run.total_reads, (unsigned long long)run.total_cor);
+    if (run.weak_ends)
+        fprintf(stderr, "Weak ends (k-mers counted below %d): %llu reads with a bad prefix, %llu with a bad suffix, %llu without a solid k-mer\n", run.weak_min,
+                (unsigned long long)run.weak_prefix, (unsigned long long)run.weak_suffix, (unsigned long long)run.weak_nosolid);
     if (report) {  // the contexts' reports, added up
         std::vector<rc_change_report> part(1), sum(1);
         memset(&sum[0], 0, sizeof sum[0]);
