@@ -268,6 +268,55 @@ int rc_weak_profile_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_
  * No reference counterpart: the dormant fields of Reads.h:20,371-372,396-412. */
 int rc_weak_profile_into(rc_ctx *ctx, int slot, rc_read_weak *out, int32_t min_count);
 
+/* ---- duplicate census: how many reads / pairs are exact copies of one another, before and after correction ------------------
+ * A UNIT is a read (mode 0) or a pair (mode 1: read r of the first half and read r of the second; mode 2: reads 2u and 2u + 1 --
+ * the mates of the correction report).  Two units are duplicates when their base strings are byte for byte equal: equal
+ * length, N / lower case / any other byte compared as it is, mate 1 with mate 1 and mate 2 with mate 2 -- no reverse
+ * complement, (a, b) is not (b, a), ("AC", "GT") is not ("ACG", "T"); qualities and names play no part.
+ * While a census is open on a context, every batch that completes on it -- rc_correct_batch, rc_correct_batch_traced, rc_wait,
+ * rc_wait_packed, rc_wait_resident (the batches of slots that run in lanes included) and rc_correct_device (in stream order,
+ * at the end of the call) -- leaves one 128-bit key per unit and version: BEFORE, of the bases as they were in HBM in front of
+ * the first correction kernel, and AFTER, of the bases as corrected (an unfixable read keeps its bases and counts like any
+ * other).  Each batch once: a packed or resident batch that came back with RC_STATUS_NOSPACE counts when its resubmission
+ * completes.  The keys of all batches stay in HBM, 16 bytes per unit and version, until end.  Equality is decided on the key
+ * alone (two independent 64-bit hashes of the bytes, the chunk order, the length, the mate and the split between the mates:
+ * rc_dups.h); two different units with one key would be counted as copies, which for n units happens with probability about
+ * n^2 / 2^129.  No census open, those calls launch, copy and allocate nothing for it; open or not, the corrected reads,
+ * ret / l / m / h, rc_summary and rc_table_digest are the same.
+ *   units             units seen
+ *   distinct_x        distinct units of version x
+ *   copies_x[c]       c = 1 .. max_bin: distinct units that occur exactly c times; the last entry: max_bin times or more (as
+ *                     rc_table_spectrum folds); copies_x[0] = 0.  The caller's arrays, max_bin + 1 entries each.
+ * So sum(copies_x) == distinct_x, and sum(c * copies_x[c]) == units while nothing reached the last entry.
+ * begin: RC_STATUS_STATE if open already (needs no table).  get: waits for what is outstanding on the context and its lanes,
+ * sorts a copy of the keys and counts the runs; the keys stay, the census stays open and goes on accumulating, any number of
+ * gets; RC_STATUS_STATE if not open, RC_STATUS_ARG: max_bin < 1 or a null pointer.  end: closes and frees (rc_destroy does
+ * too); RC_STATUS_STATE if not open; a batch in flight across end is in no census.  Where the key buffers cannot grow, the
+ * call that completes the batch returns RC_STATUS_NOSPACE with a message -- a census is never silently short.  A census holds
+ * at most 2^32 - 1 units (its sort indexes them with 32 bits; 64 GiB of keys per version): the batch that would pass that
+ * returns RC_STATUS_NOSPACE too.  While a census is open rc_correct_device BLOCKS: it returns when the batch's kernels have run
+ * and its keys are in the census (without one it stays asynchronous); the waits block as they always do.  Threads: begin, get,
+ * end and merge are the caller's to serialise against each other and against submits and waits on the same context; submits
+ * and waits of different slots may run on different threads as before (the lanes append under a mutex).  Open, the key
+ * kernel reads the arena in aligned 16-byte pieces: rc_correct_device's d_seq is read (never written) up to 15 bytes in front
+ * of its first and behind its last byte, within the 16-byte granules those bytes lie in.  No reference counterpart. */
+typedef struct {
+    uint64_t units, distinct_before, distinct_after;
+    uint64_t *copies_before, *copies_after; /* the caller's, max_bin + 1 entries each */
+} rc_dup_census;
+int rc_dup_census_begin(rc_ctx *ctx);
+int rc_dup_census_get(rc_ctx *ctx, uint32_t max_bin, rc_dup_census *out);
+int rc_dup_census_end(rc_ctx *ctx);
+/* The keys of an arena in HBM as it is: d_keys[2 u], d_keys[2 u + 1] for unit u (n_reads reads, read r the NUL-terminated
+ * string at d_off[r], d_off has n_reads + 1 entries; mode 0: n_reads units, modes 1 and 2: n_reads / 2).  Asynchronous on the
+ * context's stream (rc_sync() to wait); needs neither a table nor an open census.  RC_STATUS_ARG: a mode outside 0..2, an odd
+ * n_reads in modes 1 and 2, a null pointer with n_reads > 0, an arena of 4 GiB or more.  No reference counterpart. */
+int rc_read_keys_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_off, uint32_t n_reads, uint64_t nbytes, int mode, uint64_t *d_keys);
+/* Appends the keys src has accumulated to dst's (both open; src keeps its own): device to device where the two are on one
+ * device or peers, else through the host.  What several GPUs' contexts do at the end of a run.  RC_STATUS_STATE: either one
+ * not open; RC_STATUS_ARG: dst == src.  No reference counterpart. */
+int rc_dup_census_merge(rc_ctx *dst, rc_ctx *src);
+
 /* ---- run parameters (globals of main.cpp:17-30) ----------------------------------------------- */
 /* replaces main.cpp:310-358 (ERROR_RATE estimation).  Uses the entries parsed by the last
  * rc_table_load_jfdump() in file order -- or, for a table that was counted here or built from

@@ -19,6 +19,7 @@ ABI_SYMBOLS = [
     "rc_recount_begin", "rc_recount_add", "rc_recount_add_device", "rc_recount_follow", "rc_recount_finish",
     "rc_change_report_begin", "rc_change_report_get", "rc_change_report_end",
     "rc_weak_profile_device", "rc_weak_profile_into",
+    "rc_dup_census_begin", "rc_dup_census_get", "rc_dup_census_end", "rc_read_keys_device", "rc_dup_census_merge",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
@@ -93,6 +94,12 @@ class _ReadWeak(C.Structure):
     _fields_ = [("weak", C.c_int32), ("bad_prefix", C.c_int32), ("bad_suffix", C.c_int32), ("uncovered", C.c_int32)]
 
 
+class _DupCensus(C.Structure):
+    """rc_dup_census: three counts and the caller's two arrays of max_bin + 1 uint64"""
+    _fields_ = [("units", C.c_uint64), ("distinct_before", C.c_uint64), ("distinct_after", C.c_uint64),
+                ("copies_before", C.c_void_p), ("copies_after", C.c_void_p)]
+
+
 class _DeviceBatch(C.Structure):
     _fields_ = [("mode", C.c_int), ("n_reads", C.c_uint32), ("nbytes", C.c_uint64),
                 ("max_read_len", C.c_int32),
@@ -153,6 +160,7 @@ def load_library():
     L.rc_table_replicate.argtypes = [vp, vp]
     L.rc_table_replicate_async.argtypes = [vp, vp]
     L.rc_device_numa_node.argtypes = [vp]
+    L.rc_device_memory.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rc_table_lookup.argtypes = [vp, vp, sz, vp]
     L.rc_table_export.argtypes = [vp, vp, vp, sz, C.POINTER(C.c_size_t)]
     L.rc_table_digest.argtypes = [vp, C.POINTER(C.c_uint64)]
@@ -170,6 +178,11 @@ def load_library():
     L.rc_change_report_end.argtypes = [vp]
     L.rc_weak_profile_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, vp]
     L.rc_weak_profile_into.argtypes = [vp, C.c_int, vp, C.c_int32]
+    L.rc_dup_census_begin.argtypes = [vp]
+    L.rc_dup_census_get.argtypes = [vp, C.c_uint32, C.POINTER(_DupCensus)]
+    L.rc_dup_census_end.argtypes = [vp]
+    L.rc_read_keys_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int, vp]
+    L.rc_dup_census_merge.argtypes = [vp, vp]
     L.rc_estimate_error_rate.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.rc_bad_quality_from_hist.restype = C.c_char
     L.rc_bad_quality_from_hist.argtypes = [vp, vp, C.c_int32]
@@ -460,6 +473,37 @@ class Context:
     def weak_profile_withdraw(self, slot):
         """rc_weak_profile_into(out = NULL): the next batch of `slot` is not profiled after all"""
         self._ck(self._L.rc_weak_profile_into(self._h, int(slot), None, 1))
+
+    # ---- duplicate census: exact copies among the reads / pairs, before and after correction ----
+    def dup_census_begin(self):
+        """rc_dup_census_begin: from now on every batch that completes on this context (any batch entry point, slot lanes
+        included) leaves a 128-bit key per unit (a read; a pair in modes 1 and 2) of its bases as uploaded and as corrected."""
+        self._ck(self._L.rc_dup_census_begin(self._h))
+
+    def dup_census(self, max_bin=10000):
+        """rc_dup_census_get: {"units", "distinct_before", "distinct_after": int; "copies_before", "copies_after": uint64 arrays
+        of max_bin + 1 -- entry c: distinct units that occur exactly c times, the last one max_bin times or more}.  The census
+        stays open and cumulative; the keys are kept."""
+        before = np.zeros(int(max_bin) + 1, dtype=np.uint64)
+        after = np.zeros(int(max_bin) + 1, dtype=np.uint64)
+        r = _DupCensus(0, 0, 0, before.ctypes.data, after.ctypes.data)
+        self._ck(self._L.rc_dup_census_get(self._h, int(max_bin), C.byref(r)))
+        return {"units": int(r.units), "distinct_before": int(r.distinct_before), "distinct_after": int(r.distinct_after),
+                "copies_before": before, "copies_after": after}
+
+    def dup_census_end(self):
+        """rc_dup_census_end: closes the census and frees the keys."""
+        self._ck(self._L.rc_dup_census_end(self._h))
+
+    def read_keys_device(self, d_seq, d_off, n_reads, nbytes, mode, d_keys):
+        """rc_read_keys_device: the keys of an arena in HBM as it is; d_keys: device memory (16-byte aligned) for two uint64 per
+        unit -- n_reads units in mode 0, n_reads / 2 pairs in modes 1 and 2.  Asynchronous: sync() to wait."""
+        self._ck(self._L.rc_read_keys_device(self._h, _ptr(d_seq), _ptr(d_off), n_reads, nbytes, int(mode), _ptr(d_keys)))
+
+    def dup_census_merge(self, other):
+        """rc_dup_census_merge: appends the keys `other` (a Context with an open census, on any device) has accumulated to this
+        context's; other keeps its own."""
+        self._ck(self._L.rc_dup_census_merge(self._h, other._h))
 
     # ---- run parameters ----
     def estimate_error_rate(self, wk=0.95):

@@ -14,10 +14,28 @@ int rc_probe_device(rc_ctx *ctx, const uint8_t *d_seq, uint64_t nbytes, int32_t 
 
 
 // (the correction report: rc_correct_device has no wait -- the batch counts at the end of the call, in stream order)
+// (the duplicate census: the batch's keys go to scratch of the context; `commit`: into the census at the end of the call,
+// which then returns when they are in -- rc_correct_batch_traced commits where its batch completes instead)
+static int correct_device_census(rc_ctx *ctx, const rc_device_batch *b, bool commit)
+{
+    if (!ctx || !b) return RC_ERR_ARG;
+    const bool keyed = ctx->dup_open && b->n_reads && b->mode >= 0 && b->mode <= 2 && b->d_seq && b->d_off && b->nbytes < (1ull << 32) &&
+                       !(b->mode != 0 && (b->n_reads & 1u));  // (what rc_correct_device_impl refuses is refused there, unkeyed)
+    int rc;
+    ctx->dup_tmp_units = 0;
+    if (keyed) {
+        RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+        if ((rc = rc_dups_stage(ctx, b, 0, &ctx->dup_tmp, &ctx->dup_tmp_units, &ctx->dup_tmp_gen))) return rc;
+    }
+    if ((rc = rc_correct_device_impl(ctx, b, 0xFFFFFFFFu, 0))) return rc;
+    if ((rc = rc_report_count(ctx, b, 0xFFFFFFFFu, 0, -1, nullptr, nullptr))) return rc;
+    if (keyed && (rc = rc_dups_stage(ctx, b, 1, &ctx->dup_tmp, &ctx->dup_tmp_units, &ctx->dup_tmp_gen))) return rc;
+    return commit ? rc_dups_commit(ctx, &ctx->dup_tmp, &ctx->dup_tmp_units, ctx->dup_tmp_gen) : RC_OK;
+}
+
 int rc_correct_device(rc_ctx *ctx, const rc_device_batch *b)
 {
-    const int rc = rc_correct_device_impl(ctx, b, 0xFFFFFFFFu, 0);
-    return rc ? rc : rc_report_count(ctx, b, 0xFFFFFFFFu, 0, -1, nullptr, nullptr);
+    return correct_device_census(ctx, b, true);
 }
 
 // qual_split / qual_base2 (quality-bit mode only): arena bytes from qual_split on have their bits at
@@ -385,7 +403,7 @@ static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t)
     }
     RC_CHECK_HIP(ctx, hipMemcpyAsync(ctx->h_off.p, off.data(), (total_reads + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     const rc_device_batch db = rc_device_batch_over(b->mode, total_reads, nbytes, max_len, d_seq, d_qual, (const uint32_t *)ctx->h_off.p, (int32_t *)ctx->h_res.p);
-    if ((rc = rc_correct_device(ctx, &db))) return rc;
+    if ((rc = correct_device_census(ctx, &db, false))) return rc;
     RC_CHECK_HIP(ctx, hipMemcpyAsync(b->seq, d_seq, bytes1, hipMemcpyDeviceToHost, ctx->stream));
     if (b->mode == 1) RC_CHECK_HIP(ctx, hipMemcpyAsync(b->seq2, d_seq + bytes1, bytes2, hipMemcpyDeviceToHost, ctx->stream));
     RC_CHECK_HIP(ctx, hipMemcpyAsync(b->ret, db.d_ret, total_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -409,7 +427,8 @@ static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t)
         }
     }
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return rc_recount_take(ctx, d_seq, nbytes);  // (rc_recount_follow: the traced entry point's batches complete here)
+    if ((rc = rc_recount_take(ctx, d_seq, nbytes))) return rc;  // (rc_recount_follow: the traced entry point's batches complete here)
+    return rc_dups_commit(ctx, &ctx->dup_tmp, &ctx->dup_tmp_units, ctx->dup_tmp_gen);  // (the duplicate census: likewise)
 }
 
 }  // extern "C"

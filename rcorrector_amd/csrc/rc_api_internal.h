@@ -79,6 +79,11 @@ struct rc_slot {
     bool weak_pinned = false;
     rc_dbuf d_weak;
     rc_hbuf p_weak;
+    // duplicate census: the keys of the batch in flight, dup_units before | dup_units after, until its wait accepts it
+    // (dup_units == 0: none were taken); dup_gen: the census they were taken for
+    rc_dbuf d_dup;
+    size_t dup_units = 0;
+    uint64_t dup_gen = 0;
     uint32_t fix_room = 0;
     bool fix_pinned = false;
 };
@@ -145,4 +150,12 @@ int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes);
 int rc_report_count(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits, rc_dbuf *staged, bool *did);
 int rc_report_commit(rc_ctx *ctx, const rc_dbuf *staged);
 void rc_report_release(rc_ctx *ctx);
+// rc_api_dups.hip -- the duplicate census.  ctx is the context the batch runs in (a context or one of its slot lanes); the
+// census is that of the context the batch was submitted to.  All do nothing while no census is open.
+// stage: the keys of the batch's arena as it is now, on ctx's stream, into keys (version 0: before the first correction
+// kernel -- reserves keys for both versions and sets *units / *gen; version 1: behind the last one).  commit: a completed
+// batch's staged keys appended to the census, complete on return; *units = 0 afterwards.
+int rc_dups_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_dbuf *keys, size_t *units, uint64_t *gen);
+int rc_dups_commit(rc_ctx *ctx, const rc_dbuf *keys, size_t *units, uint64_t gen);
+void rc_dups_release(rc_ctx *ctx);
 }

@@ -155,6 +155,17 @@ bool write_histo(const char *path, const std::vector<uint64_t> &freq)
     return fclose(fp) == 0 && ok;
 }
 
+bool write_dup_census(const char *path, const rc_dup_census &D, uint32_t max_bin, const char *unit)
+{
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return false;
+    typedef unsigned long long ull;
+    bool ok = fprintf(fp, "units\t%llu\t%s\ndistinct\tbefore\t%llu\ndistinct\tafter\t%llu\n", (ull)D.units, unit, (ull)D.distinct_before, (ull)D.distinct_after) > 0;
+    for (uint32_t c = 1; c <= max_bin && ok; ++c)
+        if (D.copies_before[c] || D.copies_after[c]) ok = fprintf(fp, "copies\t%u\t%llu\t%llu\n", c, (ull)D.copies_before[c], (ull)D.copies_after[c]) > 0;
+    return fclose(fp) == 0 && ok;
+}
+
 bool write_change_report(const char *path, const rc_change_report &R, bool two_mates)
 {
     FILE *fp = fopen(path, "wb");

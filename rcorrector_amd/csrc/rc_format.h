@@ -175,6 +175,10 @@ bool write_histo(const char *path, const std::vector<uint64_t> &freq);
 //   and pos3 <mate> <distance from the last base, 1 = the last base> <changes>, a line per position up to the mate's longest
 //   read / subst <A|C|G|T|N> <A|C|G|T> <count>, all 20 / qual <low|high|none> <count> / perread <n | 64+> <reads>, non-zero ones
 bool write_change_report(const char *path, const rc_change_report &R, bool two_mates);
+// the duplicate census (rcorrector_amd.h: rc_dup_census, binned to max_bin) as tab-separated text: units <n> <unit> / distinct
+// before <n> / distinct after <n> / copies <c> <distinct before> <distinct after>, a line per c where either is non-zero (the
+// line of c = max_bin: that many copies or more)
+bool write_dup_census(const char *path, const rc_dup_census &D, uint32_t max_bin, const char *unit);
 // GetBadQuality's two histograms over the records of one block (main.cpp:88-128), at most `room` of them
 void quality_histograms(const Block &b, int lpr, size_t room, std::vector<int32_t> &fh, std::vector<int32_t> &lh, int *total);
 

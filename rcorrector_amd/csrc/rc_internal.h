@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -164,6 +165,19 @@ struct rc_ctx {
     };
     rc_dbuf weak_planes;
     rc_weak_reg weak_reg[4], weak_cur;
+    // duplicate census (rc_dup_census_begin; kernels in rc_dups.hip).  In the context it was opened on (the batches of its slot
+    // lanes add to it too: lane_parent): the keys of every unit seen, version 0 = before and 1 = after correction, 16 bytes per
+    // unit each, dup_n units of dup_cap; dup_gen counts the begins (keys a batch staged for one census never reach the next).
+    // dup_mutex: the lanes' waits append concurrently.  In the context a batch RUNS in: dup_tmp, the keys (before | after) of
+    // the batch of an entry point that has no slot (rc_correct_device, rc_correct_batch_traced), dup_tmp_units of them
+    std::atomic<bool> dup_open{false};  // (read by the lanes' submits without the mutex)
+    void *dup_acc[2] = {nullptr, nullptr};
+    size_t dup_n = 0, dup_cap = 0;
+    uint64_t dup_gen = 0;
+    std::mutex dup_mutex;
+    rc_dbuf dup_tmp;
+    size_t dup_tmp_units = 0;
+    uint64_t dup_tmp_gen = 0;
 
     // batch scratch
     rc_dbuf counts;   // int32 per arena byte
@@ -297,6 +311,12 @@ int rc_launch_report_commit(rc_ctx *ctx, const unsigned long long *d_staged, uns
 // rc_weak.hip: solid / weak bit planes of the arena into `planes` (grow-only), then d_out[r] = the rc_read_weak of read r
 int rc_launch_weak_profile(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int min_count, rc_dbuf *planes,
                            void *d_out);
+
+// rc_dups.hip: one 128-bit key per unit of an arena (mode as rc_device_batch: n_reads units, or n_reads / 2 pairs) on stream st;
+// the census of n keys in HBM (left as they are) into host arrays copies[max_bin + 1], *distinct -- synchronous
+int rc_launch_read_keys(rc_ctx *ctx, hipStream_t st, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int mode,
+                        uint64_t *d_keys);
+int rc_dup_census_run(rc_ctx *ctx, const uint64_t *d_keys, size_t n, uint32_t max_bin, uint64_t *copies, uint64_t *distinct);
 
 // rc_transport.hip: the packed boundary (include/rcorrector_amd.h: rc_packed_batch)
 int rc_launch_unpack(rc_ctx *ctx, const uint32_t *d_packed, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, const uint32_t *d_exc_pos,

@@ -27,6 +27,8 @@
 // substitutions by position, letters, quality class, mate and read, counted on the GPU as the batches complete.
 // -weak-ends tags every record with the reference's dormant bad_prefix= / bad_suffix= fields (Reads.h:396-412), filled from the
 // weak-k-mer profile of the corrected reads (rcorrector_amd.h: rc_read_weak; -weak-min: the count below which a k-mer is weak).
+// -dups FILE writes the duplicate census (rcorrector_amd.h: rc_dup_census; rc_format.h: write_dup_census): how many reads or
+// pairs are exact copies of one another, as uploaded and as corrected, from 128-bit keys taken on the GPU as the batches complete.
 #include <fcntl.h>
 #include <malloc.h>
 #include <sys/stat.h>
@@ -75,6 +77,13 @@ static void print_help()
             "\t\tnothing is trimmed; one more line on stderr counts the reads with a bad prefix, a bad suffix, and no such k-mer at all\n"
             "\t\t(every read counts there, unfixable ones included); not with -verbose\n"
             "\t-weak-min INT: with -weak-ends, a k-mer counted fewer times than this in the table is weak (default: 1)\n"
+            "\t-dups STRING: also write the duplicate census, tab-separated text: the units (reads, or pairs for -1/-2 and -i input), the\n"
+            "\t\tdistinct units before and after correction, and for every number of copies c the distinct units that occur c times,\n"
+            "\t\tbefore and after; two units are copies when their bases are byte for byte equal (mate 1 with mate 1, mate 2 with\n"
+            "\t\tmate 2, no reverse complement); one more line on stderr gives the duplicate fraction; the keys (32 bytes per unit) stay\n"
+            "\t\tin GPU memory until the end of the run, at most 2^32 - 1 units; with -gpus above 1 the GPUs' keys are merged on the\n"
+            "\t\tfirst; the input is all single-end or all paired (-p / -i), not a mix; not with -verbose\n"
+            "\t-dups-max INT: with -dups, units with this many copies or more are counted in the last line (default: 10000)\n"
             "\t-verbose-iter INT: threshold iterations recorded per read for -verbose (default: 64)\n");
 }
 
@@ -87,7 +96,8 @@ int main(int argc, char **argv)
     std::vector<ReadFile> &files = run.files, &mates = run.mates;
     int max_fix_per_k = 4, i;
     double wk = 0.95;
-    const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr, *report = nullptr;
+    const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr, *report = nullptr, *dups = nullptr;
+    long dups_max = 10000;
     long histo_max = 10000;
     std::string od = "./";
     bool verbose = false;
@@ -145,6 +155,10 @@ int main(int argc, char **argv)
             histo_after = argv[++i];
         else if (!strcmp("-report", argv[i]))
             report = argv[++i];
+        else if (!strcmp("-dups", argv[i]))
+            dups = argv[++i];
+        else if (!strcmp("-dups-max", argv[i]))
+            dups_max = atol(argv[++i]);
         else if (!strcmp("-weak-ends", argv[i]))
             run.weak_ends = true;
         else if (!strcmp("-weak-min", argv[i]))
@@ -161,6 +175,8 @@ int main(int argc, char **argv)
     }
     g_verbose = verbose;
     if (run.weak_ends && verbose) die("rcorrector: usage: -weak-ends cannot be combined with -verbose (the transcript's entry point takes no weak-k-mer profile)\n");
+    if (dups && verbose) die("rcorrector: usage: -dups cannot be combined with -verbose (small batches through the transcript's entry point: run the census without it)\n");
+    if (dups && (dups_max < 1 || dups_max > (1l << 28))) die("rcorrector: usage: -dups-max must be 1..%ld\n", 1l << 28);
     if (run.weak_min < 1) die("rcorrector: usage: -weak-min must be at least 1\n");
     if (g_trace_iter < 1) g_trace_iter = 1;
     // -verbose carries RC_TRACE_ITER_WORDS x trace-iter words per read through host and device
@@ -500,6 +516,17 @@ int main(int argc, char **argv)
         for (int c = 0; c < nctx; ++c)
             if (rc_change_report_begin(ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
 
+    // -dups: every context keeps the keys of the batches that complete on it, whatever the transport
+    if (dups) {
+        size_t two = 0;
+        for (const ReadFile &f : files) two += f.paired || f.interleaved;
+        if (two && two != files.size())
+            die("rcorrector: usage: -dups counts reads or pairs, not both in one census: give single-end files (-r) or paired ones (-p / -i), not a mix\n");
+    }
+    if (dups)
+        for (int c = 0; c < nctx; ++c)
+            if (rc_dup_census_begin(ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+
     // pipeline: reader (this thread) -> `inflight` workers per GPU -> writer thread (input order)
     warm.join();
     stamp("batch buffers ready");
@@ -548,6 +575,25 @@ int main(int argc, char **argv)
         bool two_mates = false;
         for (const ReadFile &f : files) two_mates = two_mates || f.paired || f.interleaved;
         if (!write_change_report(report, sum[0], two_mates)) die("rcorrector: could not write %s\n", report);
+    }
+    if (dups) {  // the contexts' keys, merged into the first
+        const double td0 = now_s();
+        for (int c = 1; c < nctx; ++c)
+            if (rc_dup_census_merge(ctx[0], ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+        std::vector<uint64_t> before((size_t)dups_max + 1), after((size_t)dups_max + 1);
+        rc_dup_census dc;
+        dc.copies_before = before.data();
+        dc.copies_after = after.data();
+        if (rc_dup_census_get(ctx[0], (uint32_t)dups_max, &dc)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+        size_t two = 0;
+        for (const ReadFile &f : files) two += f.paired || f.interleaved;
+        const char *unit = two ? "pairs" : "reads";  // (all of one kind: checked before the run)
+        if (!write_dup_census(dups, dc, (uint32_t)dups_max, unit)) die("rcorrector: could not write %s\n", dups);
+        if (g_timing) fprintf(stderr, "[rc timing] -dups: merge, sort and census %.2f s\n", now_s() - td0);
+        const double u = dc.units ? (double)dc.units : 1.0;
+        fprintf(stderr, "Duplicates: %llu %s, %llu distinct before correction (duplicate fraction %.4f), %llu after (%.4f)\n", (unsigned long long)dc.units, unit,
+                (unsigned long long)dc.distinct_before, dc.units ? 1.0 - (double)dc.distinct_before / u : 0.0, (unsigned long long)dc.distinct_after,
+                dc.units ? 1.0 - (double)dc.distinct_after / u : 0.0);
     }
     if (histo_after) {
         const double th0 = now_s();
