@@ -75,6 +75,7 @@ int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_
     a.mode = b->mode;
     a.n = b->n_reads;
     a.seq = b->d_seq;
+    a.nbytes = (size_t)b->nbytes;
     a.qual = b->d_qual;
     a.qual_bits = qual_bits >= 0 ? qual_bits : (ctx->qual_bits ? 1 : 0);
     a.qual_split = qual_split;
@@ -213,6 +214,7 @@ int rc_strong_threshold_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t
     a.mode = 0;
     a.n = n_reads;
     a.seq = const_cast<uint8_t *>(d_seq);
+    a.nbytes = (size_t)nbytes;
     a.off = d_off;
     a.max_len = max_read_len;
     if ((rc = rc_launch_probe(ctx, d_seq, (size_t)nbytes, (int32_t *)ctx->counts.p))) return rc;
@@ -258,6 +260,7 @@ static int one_read_upload(rc_ctx *ctx, const char *seq, const char *qual, rc_de
     a.mode = 0;
     a.n = 1;
     a.seq = (uint8_t *)ctx->h_seq.p;
+    a.nbytes = n1;
     a.qual = (const uint8_t *)ctx->h_qual.p;
     a.off = (const uint32_t *)ctx->h_off.p;
     a.ret = d_res;

@@ -48,6 +48,7 @@ int rc_report_count(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, 
     a.mode = b->mode;
     a.n = b->n_reads;
     a.seq = b->d_seq;
+    a.nbytes = (size_t)b->nbytes;
     a.qual = b->d_qual;
     a.qual_bits = qual_bits >= 0 ? qual_bits : (ctx->qual_bits ? 1 : 0);
     a.qual_split = qual_split;

@@ -12,6 +12,7 @@
 // container, so the wave-uniform control flow of the search kernel is first checked against the
 // oracle on the CPU).  RC_HD is the only portability hook.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -181,6 +182,62 @@ RC_HD void rc_pack16m(const uint32_t (&w)[4], uint32_t &code, uint32_t &am, uint
     bad = rc_compress_even16(rb >> 1);
     tm = rc_compress_even16(r & (r >> 1)) & ~bad;
     am = rc_compress_even16(~(r | (r >> 1)));
+}
+
+// a letter as rc_read_state::base holds it: 0 1 2 3 = A C G T, 4 = N, 5 = anything else
+RC_HD int rc_base_code(uint32_t c)
+{
+    int b = 5;
+    b = c == 'A' ? 0 : b;
+    b = c == 'C' ? 1 : b;
+    b = c == 'G' ? 2 : b;
+    b = c == 'T' ? 3 : b;
+    b = c == 'N' ? 4 : b;
+    return b;
+}
+
+// ---- a read's bytes, 16 at a time, for k_single (rc_single.h: rcs_row) ------------------------------------------------------
+// rc_stage16: bytes [16 j, 16 j + 16) of the read that starts at arena byte o and is len bytes long, as four dwords (first byte in
+// the low bits), bytes at or past len as 0.  Aligned dword loads from (o + 16 j) & ~3 on -- five of them where the group starts
+// inside a dword, funnel-shifted into place -- and only of dwords that hold a byte of the read; no load addresses a byte outside
+// [a, a + nbytes): a dword that would run past nbytes (the arena's last one, when nbytes is no multiple of 4) is read byte by byte.
+// a is 4-byte aligned (the fused probe kernel's staging assumes the same of the arena).  Any o, any len: 151-byte strides, ragged
+// batches.  rc_pack16m takes the four dwords as they are: the 0 bytes behind the read's end are "not a base" (code 3, bad).
+// tests/hostmath/stage_wide.cpp: against a byte-at-a-time restatement, on an arena of exactly nbytes bytes.
+RC_HD uint32_t rc_load_dword_in(const uint8_t *a, uint32_t nbytes, uint32_t at)  // at % 4 == 0, at < nbytes
+{
+    if (nbytes - at >= 4u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return *reinterpret_cast<const uint32_t *>(a + at);
+#else
+        return (uint32_t)a[at] | ((uint32_t)a[at + 1] << 8) | ((uint32_t)a[at + 2] << 16) | ((uint32_t)a[at + 3] << 24);
+#endif
+    }
+    uint32_t v = 0;
+    for (uint32_t q = 0; q < nbytes - at; ++q) v |= (uint32_t)a[at + q] << (8 * q);
+    return v;
+}
+RC_HD void rc_stage16(const uint8_t *a, size_t nbytes, uint32_t o, int len, int j, uint32_t (&w)[4])
+{
+    // (32-bit offsets: an arena is below 4 GiB -- rc_correct_device_impl -- and the read lies inside it, so neither g0 nor a dword
+    // that is loaded wraps; a group past the read's end has left <= 0 and loads nothing whatever g0 is)
+    const int left = len - 16 * j;  // bytes of the read from the group's first byte on
+    const uint32_t g0 = o + 16u * (uint32_t)j, ab = g0 & ~3u, sh = 8u * (g0 & 3u);
+    const int want = (left < 16 ? (left > 0 ? left : 0) : 16) + (int)(g0 & 3u);  // bytes from ab on that end the group's part of the read
+    uint32_t d[5];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) d[q] = 4 * q < want && left > 0 ? rc_load_dword_in(a, (uint32_t)nbytes, ab + 4u * (uint32_t)q) : 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        uint32_t x = __builtin_amdgcn_alignbit(d[q + 1], d[q], sh);
+#else
+        uint32_t x = sh ? (d[q] >> sh) | (d[q + 1] << (32u - sh)) : d[q];
+#endif
+        const int nb = left - 4 * q;  // bytes of this dword inside the read
+        if (nb < 4) x = nb <= 0 ? 0u : x & (0xFFFFFFFFu >> (8 * (4 - nb)));
+        w[q] = x;
+    }
 }
 
 // reverse complement of a k-mer code (first base in the most significant 2 bits, as the

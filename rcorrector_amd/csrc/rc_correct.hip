@@ -489,6 +489,7 @@ static int fill_args(rc_ctx *ctx, const rc_device_batch_args &a, rc_kernel_args 
     A.mode = a.mode;
     A.n = a.n;
     A.seq = a.seq;
+    A.nbytes = a.nbytes;
     A.qual = a.qual;
     A.qual_bits = a.qual_bits;
     A.qual_split = a.qual_split;

@@ -466,23 +466,13 @@ __device__ __forceinline__ void rc_carve(uint8_t *lds, const rc_lds_layout &L, r
     S.memo = S.spec_meta + 4;
 }
 
-__device__ __forceinline__ int rc_base_code(uint32_t c)
-{
-    int b = 5;
-    b = c == 'A' ? 0 : b;
-    b = c == 'C' ? 1 : b;
-    b = c == 'G' ? 2 : b;
-    b = c == 'T' ? 3 : b;
-    b = c == 'N' ? 4 : b;
-    return b;
-}
-
 struct rc_kernel_args {
     rc_table_view T;
     rc_run_params P;
     int mode;
     uint32_t n;
     uint8_t *seq;
+    size_t nbytes;         // bytes of the arena seq: rc_stage16 (k_single) loads dwords, none past this
     const uint8_t *qual;   // one byte per arena byte, or (qual_bits) one BIT per arena byte: quality > badQualityThreshold
     int qual_bits;
     uint32_t qual_split, qual_base2;  // bit mode: arena bytes >= qual_split have their bits at byte qual_base2 on (second arena of a host batch)

@@ -282,6 +282,7 @@ struct rc_device_batch_args {
     int mode;            // 0 single, 1 paired (reads [0,n/2) are mates of [n/2,n)), 2 interleaved
     uint32_t n;          // reads
     uint8_t *seq;        // arena, reads NUL-terminated
+    size_t nbytes = 0;   // bytes of the arena: no kernel reads a byte at or past it
     const uint8_t *qual; // same offsets (or one bit per arena byte, see rc_set_quality_bits)
     int qual_bits = 0;
     uint32_t qual_split = 0xFFFFFFFFu, qual_base2 = 0;

@@ -120,7 +120,8 @@ __device__ __forceinline__ void rcs_row(const rc_kernel_args &A, uint32_t r, int
         ok = ns >= 1 && ns <= max_seg;
     }
     if (!__ballot(ok)) return;  // (no row of this wave has a read: nothing below touches another wave)
-    // the packed read (ds_or of every base's two bits) and K1's counts -> the row's LDS
+    // the packed read and K1's counts -> the row's LDS
+#ifdef RC_STAGE_BYTEWISE  // the former staging: a byte per lane per pass, ds_or of every base's two bits
     if (l < PK_WORDS) s_pk_row[l] = 0;
     wsync();
 #pragma unroll
@@ -135,6 +136,38 @@ __device__ __forceinline__ void rcs_row(const rc_kernel_args &A, uint32_t r, int
         if (ok && g < kcnt) v = A.counts[o + g];
         s_cnt_row[g] = v;
     }
+#else
+    // sixteen bases per lane (rc_common.h: rc_stage16 / rc_pack16m, the fused probe kernel's packer): lane j of the row
+    // stores the code word of group j -- a candidate has ACGT letters only, and no window the code below asks for reaches
+    // past the read's end, where the packer puts 3 -- and the counts come as int4 from (o & ~3) on, as the fused probe kernel
+    // stored them (rc_correct.hip; the words in front of the first count and behind the last one are not used)
+    wsync();
+    if (l < PK_WORDS) {
+        uint32_t code = 0;
+        if (ok && l < PK_WORDS - 2) {
+            uint32_t v[4], am, tm, bad;
+            rc_stage16(A.seq, A.nbytes, o, len, l, v);
+            rc_pack16m(v, code, am, tm, bad);
+        }
+        s_pk_row[l] = code;
+    }
+    {
+        const int head = (int)(o & 3u);
+        const int4 *c4 = reinterpret_cast<const int4 *>(A.counts + (o - (uint32_t)head));
+#pragma unroll
+        for (int e = 0; e < (MAX_KCNT + 6 + 63) / 64; ++e) {  // int4 number q holds counts 4 q - head .. 4 q - head + 3
+            const int q = e * 16 + l, i0 = 4 * q - head;  // counts[i0 .. i0 + 3] of the read
+            int4 c = make_int4(0, 0, 0, 0);
+            if (ok && i0 < kcnt) c = c4[q];
+            const int cv[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+            for (int f = 0; f < 4; ++f) {
+                const int g = i0 + f;
+                if (g >= 0 && g < MAX_KCNT) s_cnt_row[g] = g < kcnt ? cv[f] : 0;
+            }
+        }
+    }
+#endif
     wsync();
 #if defined(RC_K2S_STOP) && RC_K2S_STOP == 1  // dev builds: cost of the stages up to here
     return;
