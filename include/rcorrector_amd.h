@@ -317,6 +317,61 @@ int rc_read_keys_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_off
  * not open; RC_STATUS_ARG: dst == src.  No reference counterpart. */
 int rc_dup_census_merge(rc_ctx *dst, rc_ctx *src);
 
+/* ---- k-mer trust profile by read position: where along the reads the untrusted k-mers lie, before and after correction ------
+ * Window validity, SOLID and WEAK are exactly those of the per-read weak-k-mer profile above (rc_read_weak): at the context's
+ * k, against the context's table, at a threshold min_count >= 1.  A read of L bases has nwin = max(0, L - k + 1) windows;
+ * window i has position p5 = i from the 5' end and p3 = nwin - 1 - i from the 3' end (p3 = 0 is the last window).  A MATE is
+ * the correction report's: mode 0: every read is mate 0; mode 1: the first half of the reads is mate 0, the second half mate
+ * 1; mode 2: even reads are mate 0, odd reads mate 1.  One rc_trust_counts describes one version of the reads; per mate m:
+ *   windows[m][p]              reads that have a window p (nwin > p) -- the same number from either end
+ *   solid5[m][p], weak5[m][p]  reads whose window at p5 = p is solid / weak
+ *   solid3[m][p], weak3[m][p]  reads whose window at p3 = p is solid / weak
+ * so the invalid windows at p are windows - solid - weak, sum(solid5[m]) == sum(solid3[m]) and sum(weak5[m]) == sum(weak3[m]),
+ * and with min_count = 1 the sum of weak5 over an arena is the sum of rc_read_weak.weak over it (rc_recount_stats.absent_total
+ * of a recount of it).  A read has at most RC_TRUST_MAX_LEN windows counted (the reference's reads have at most 1023 bases,
+ * utils.h:7).  The profile only counts: nothing is trimmed, dropped or reordered.
+ * While a profile is open on a context, every batch that completes on it -- rc_correct_batch, rc_correct_batch_traced,
+ * rc_wait, rc_wait_packed, rc_wait_resident (the batches of slots that run in lanes included) and rc_correct_device (in
+ * stream order, at the end of the call) -- counts once: BEFORE from the bases as they were in HBM in front of the first
+ * correction kernel, AFTER from the bases as corrected (an unfixable read keeps its bases and counts like any other).  A
+ * packed or resident batch that came back with RC_STATUS_NOSPACE counts when its resubmission completes.  No profile open,
+ * those calls launch, copy and allocate nothing for it; open or not, the corrected reads, ret / l / m / h, rc_summary and
+ * rc_table_digest are the same.
+ * begin: RC_STATUS_STATE if open already or without a table (min_count means nothing without one), RC_STATUS_ARG: min_count <
+ * 1.  get: waits for what is outstanding on the context and its lanes, then copies the counts out; the profile stays open
+ * and goes on accumulating, any number of gets; RC_STATUS_STATE if not open, RC_STATUS_ARG: out == NULL.  end: closes and
+ * frees (rc_destroy does too); RC_STATUS_STATE if not open; a batch in flight across end is in no profile.  While a profile
+ * is open rc_correct_device BLOCKS: it returns when the batch's kernels have run and its counts are in the profile (without
+ * one it stays asynchronous); the waits block as they always do.  Threads: begin, get and end are the caller's to serialise
+ * against each other and against submits and waits on the same context; submits and waits of different slots may run on
+ * different threads as before (the lanes add under a mutex).  Open, the planes kernel reads the arena in aligned 16-byte
+ * pieces: rc_correct_device's d_seq is read (never written) up to 15 bytes in front of its first and behind its last byte,
+ * within the 16-byte granules those bytes lie in.  -weak-ends and a profile each pay their own pass over the arena.
+ * No reference counterpart. */
+#define RC_TRUST_MAX_LEN 1024
+typedef struct {                       /* one version of the reads */
+    uint64_t windows[2][RC_TRUST_MAX_LEN]; /* [mate][p]: reads that have a window p (nwin > p); the same from either end */
+    uint64_t solid5[2][RC_TRUST_MAX_LEN], weak5[2][RC_TRUST_MAX_LEN];   /* by p5 */
+    uint64_t solid3[2][RC_TRUST_MAX_LEN], weak3[2][RC_TRUST_MAX_LEN];   /* by p3 */
+} rc_trust_counts;                     /* invalid windows at p = windows - solid - weak */
+typedef struct { int32_t k, min_count; uint64_t reads[2]; rc_trust_counts before, after; } rc_trust_profile;
+/* The reads of an arena in HBM as they are: n_reads reads, read r the NUL-terminated string at d_off[r], d_off has n_reads + 1
+ * entries, mates by `mode` as above; their counts are ADDED to *d_counts, an rc_trust_counts in HBM that the caller zeroed
+ * (or that holds earlier arenas' counts).  Asynchronous on the context's stream, like rc_weak_profile_device (rc_sync() to
+ * wait); needs a table, no open profile.  d_seq is never written, and may be read in aligned 16-byte pieces up to 15 bytes
+ * in front of its first and behind its last byte, as the correction report and the weak profile do.  max_read_len, the
+ * longest read in bases, picks the kernel instance (reads of up to 256 windows keep their counters in a quarter of the
+ * registers); the kernel clamps every read's nwin to what the instance holds, at most RC_TRUST_MAX_LEN, so a wrong
+ * max_read_len can never index outside the arrays -- a read longer than it said merely has only its first windows counted.
+ * RC_STATUS_ARG: min_count < 1, a null pointer with n_reads > 0, a mode outside 0..2, mode 1 with an odd n_reads,
+ * max_read_len > RC_TRUST_MAX_LEN - 1, nbytes >= 2^32; RC_STATUS_STATE: no table.  rc_profile_get's kernels 5 (the planes) and
+ * 6 (accumulate and column sums) time it.  No reference counterpart. */
+int rc_trust_profile_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_off, uint32_t n_reads, uint64_t nbytes,
+                            int32_t max_read_len, int32_t mode, int32_t min_count, rc_trust_counts *d_counts);
+int rc_trust_profile_begin(rc_ctx *ctx, int32_t min_count);
+int rc_trust_profile_get(rc_ctx *ctx, rc_trust_profile *out);
+int rc_trust_profile_end(rc_ctx *ctx);
+
 /* ---- run parameters (globals of main.cpp:17-30) ----------------------------------------------- */
 /* replaces main.cpp:310-358 (ERROR_RATE estimation).  Uses the entries parsed by the last
  * rc_table_load_jfdump() in file order -- or, for a table that was counted here or built from
@@ -545,7 +600,8 @@ int rc_profile_correct_counters(rc_ctx *ctx, uint64_t *reads_listed, uint64_t *g
  * reads finished before that kernel are not written) -- which reads of a batch the search works hardest on
  * (MAX_TRIAL, ErrorCorrection.cpp:7; the straggler of tools/find_straggler.py).  NULL switches it off. */
 int rc_profile_read_rounds(rc_ctx *ctx, int32_t *d_rounds);
-/* kernel 0 = probe, 1 = threshold, 2 = correct, 3 = isolated substitutions, 4 = weak-k-mer profile; accumulated since the last reset */
+/* kernel 0 = probe, 1 = threshold, 2 = correct, 3 = isolated substitutions, 4 = weak-k-mer profile, 5 = the trust profile's
+ * planes, 6 = its accumulate and column sums; accumulated since the last reset */
 int rc_profile_get(rc_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
 int rc_profile_reset(rc_ctx *ctx);
 

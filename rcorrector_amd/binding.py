@@ -20,6 +20,7 @@ ABI_SYMBOLS = [
     "rc_change_report_begin", "rc_change_report_get", "rc_change_report_end",
     "rc_weak_profile_device", "rc_weak_profile_into",
     "rc_dup_census_begin", "rc_dup_census_get", "rc_dup_census_end", "rc_read_keys_device", "rc_dup_census_merge",
+    "rc_trust_profile_device", "rc_trust_profile_begin", "rc_trust_profile_get", "rc_trust_profile_end",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
@@ -98,6 +99,21 @@ class _DupCensus(C.Structure):
     """rc_dup_census: three counts and the caller's two arrays of max_bin + 1 uint64"""
     _fields_ = [("units", C.c_uint64), ("distinct_before", C.c_uint64), ("distinct_after", C.c_uint64),
                 ("copies_before", C.c_void_p), ("copies_after", C.c_void_p)]
+
+
+TRUST_MAX_LEN = 1024
+_TrustArray = (C.c_uint64 * TRUST_MAX_LEN) * 2
+TRUST_FIELDS = ("windows", "solid5", "weak5", "solid3", "weak3")
+
+
+class _TrustCounts(C.Structure):
+    """rc_trust_counts: five arrays of [2][RC_TRUST_MAX_LEN] uint64, one version of the reads"""
+    _fields_ = [(n, _TrustArray) for n in TRUST_FIELDS]
+
+
+class _TrustProfile(C.Structure):
+    """rc_trust_profile"""
+    _fields_ = [("k", C.c_int32), ("min_count", C.c_int32), ("reads", C.c_uint64 * 2), ("before", _TrustCounts), ("after", _TrustCounts)]
 
 
 class _DeviceBatch(C.Structure):
@@ -183,6 +199,10 @@ def load_library():
     L.rc_dup_census_end.argtypes = [vp]
     L.rc_read_keys_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int, vp]
     L.rc_dup_census_merge.argtypes = [vp, vp]
+    L.rc_trust_profile_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.rc_trust_profile_begin.argtypes = [vp, C.c_int32]
+    L.rc_trust_profile_get.argtypes = [vp, C.POINTER(_TrustProfile)]
+    L.rc_trust_profile_end.argtypes = [vp]
     L.rc_estimate_error_rate.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.rc_bad_quality_from_hist.restype = C.c_char
     L.rc_bad_quality_from_hist.argtypes = [vp, vp, C.c_int32]
@@ -504,6 +524,34 @@ class Context:
         """rc_dup_census_merge: appends the keys `other` (a Context with an open census, on any device) has accumulated to this
         context's; other keeps its own."""
         self._ck(self._L.rc_dup_census_merge(self._h, other._h))
+
+    # ---- k-mer trust profile by read position, before and after correction ----
+    def trust_profile_begin(self, min_count=1):
+        """rc_trust_profile_begin: from now on every batch that completes on this context (any batch entry point, slot lanes
+        included) counts, per mate and window position from either end, its solid and weak k-windows -- of its bases as
+        uploaded and as corrected.  A k-mer the table holds fewer than min_count times is weak."""
+        self._ck(self._L.rc_trust_profile_begin(self._h, int(min_count)))
+
+    def trust_profile(self):
+        """rc_trust_profile_get: {"k", "min_count": int; "reads": uint64[2]; "before", "after": dicts of the uint64 arrays
+        "windows", "solid5", "weak5", "solid3", "weak3", each (2, RC_TRUST_MAX_LEN): [mate][position]}.  The profile stays open
+        and cumulative."""
+        r = _TrustProfile()
+        self._ck(self._L.rc_trust_profile_get(self._h, C.byref(r)))
+        version = lambda c: {n: np.ctypeslib.as_array(getattr(c, n)).astype(np.uint64) for n in TRUST_FIELDS}   # noqa: E731
+        return {"k": int(r.k), "min_count": int(r.min_count), "reads": np.array(list(r.reads), dtype=np.uint64),
+                "before": version(r.before), "after": version(r.after)}
+
+    def trust_profile_end(self):
+        """rc_trust_profile_end: closes the profile and frees its counts and scratch."""
+        self._ck(self._L.rc_trust_profile_end(self._h))
+
+    def trust_profile_device(self, d_seq, d_off, n_reads, nbytes, max_read_len, mode, d_counts, min_count=1):
+        """rc_trust_profile_device: the reads of an arena in HBM as they are, ADDED to d_counts: device memory for one
+        rc_trust_counts (5 x 2 x RC_TRUST_MAX_LEN uint64: windows, solid5, weak5, solid3, weak3), zeroed by the caller.
+        Asynchronous: sync() to wait."""
+        self._ck(self._L.rc_trust_profile_device(self._h, _ptr(d_seq), _ptr(d_off), n_reads, nbytes, int(max_read_len), int(mode), int(min_count),
+                                                 _ptr(d_counts)))
 
     # ---- run parameters ----
     def estimate_error_rate(self, wk=0.95):

@@ -239,7 +239,7 @@ void rc_destroy(rc_ctx *c)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     rc_dbuf *bufs[] = {&ctx->counts, &ctx->strong, &ctx->info, &ctx->stack, &ctx->work,
                        &ctx->h_seq, &ctx->h_qual, &ctx->h_off, &ctx->h_res, &ctx->trace, &ctx->cls, &ctx->worklist, &ctx->sel_tmp,
-                       &ctx->loc_a, &ctx->loc_list, &ctx->loc_span, &ctx->tier_flag, &ctx->tier_list, &ctx->cand, &ctx->single_list, &ctx->runs, &ctx->bs_dev, &ctx->weak_planes, &ctx->dup_tmp};
+                       &ctx->loc_a, &ctx->loc_list, &ctx->loc_span, &ctx->tier_flag, &ctx->tier_list, &ctx->cand, &ctx->single_list, &ctx->runs, &ctx->bs_dev, &ctx->weak_planes, &ctx->dup_tmp, &ctx->trust_planes, &ctx->trust_part, &ctx->trust_tmp.buf};
     for (rc_dbuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (ctx->slots) {
@@ -249,7 +249,7 @@ void rc_destroy(rc_ctx *c)
             rc_hbuf *hb[] = {&sl.p_seq, &sl.p_qual, &sl.p_off, &sl.p_res, &sl.p_in, &sl.p_fix, &sl.p_nfix, &sl.p_weak};
             for (rc_hbuf *h : hb)
                 if (h->p) (void)hipHostFree(h->p);
-            rc_dbuf *db[] = {&sl.d_seq, &sl.d_qual, &sl.d_off, &sl.d_res, &sl.d_packed, &sl.d_exc, &sl.d_fix, &sl.d_rep, &sl.d_weak, &sl.d_dup};
+            rc_dbuf *db[] = {&sl.d_seq, &sl.d_qual, &sl.d_off, &sl.d_res, &sl.d_packed, &sl.d_exc, &sl.d_fix, &sl.d_rep, &sl.d_weak, &sl.d_dup, &sl.trust.buf};
             for (rc_dbuf *d : db)
                 if (d->p) (void)hipFree(d->p);
             hipEvent_t ev[] = {sl.e_h2d, sl.e_k, sl.e_done};
@@ -266,6 +266,7 @@ void rc_destroy(rc_ctx *c)
     rc_report_release(ctx);
     for (void *acc : ctx->dup_acc)  // (the duplicate census's keys; its scratch went with the buffers above)
         if (acc) (void)hipFree(acc);
+    if (ctx->trust_acc) (void)hipFree(ctx->trust_acc);  // (the trust profile's counts; its scratch went with the buffers above)
     rc_table_release(ctx);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

@@ -15,7 +15,8 @@ int rc_probe_device(rc_ctx *ctx, const uint8_t *d_seq, uint64_t nbytes, int32_t 
 
 // (the correction report: rc_correct_device has no wait -- the batch counts at the end of the call, in stream order)
 // (the duplicate census: the batch's keys go to scratch of the context; `commit`: into the census at the end of the call,
-// which then returns when they are in -- rc_correct_batch_traced commits where its batch completes instead)
+// which then returns when they are in -- rc_correct_batch_traced commits where its batch completes instead; the trust
+// profile's counts take the same way, through the context's trust_tmp)
 static int correct_device_census(rc_ctx *ctx, const rc_device_batch *b, bool commit)
 {
     if (!ctx || !b) return RC_ERR_ARG;
@@ -27,10 +28,14 @@ static int correct_device_census(rc_ctx *ctx, const rc_device_batch *b, bool com
         RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
         if ((rc = rc_dups_stage(ctx, b, 0, &ctx->dup_tmp, &ctx->dup_tmp_units, &ctx->dup_tmp_gen))) return rc;
     }
+    if ((rc = rc_trust_stage(ctx, b, 0, &ctx->trust_tmp))) return rc;
     if ((rc = rc_correct_device_impl(ctx, b, 0xFFFFFFFFu, 0))) return rc;
     if ((rc = rc_report_count(ctx, b, 0xFFFFFFFFu, 0, -1, nullptr, nullptr))) return rc;
     if (keyed && (rc = rc_dups_stage(ctx, b, 1, &ctx->dup_tmp, &ctx->dup_tmp_units, &ctx->dup_tmp_gen))) return rc;
-    return commit ? rc_dups_commit(ctx, &ctx->dup_tmp, &ctx->dup_tmp_units, ctx->dup_tmp_gen) : RC_OK;
+    if ((rc = rc_trust_stage(ctx, b, 1, &ctx->trust_tmp))) return rc;
+    if (!commit) return RC_OK;
+    if ((rc = rc_dups_commit(ctx, &ctx->dup_tmp, &ctx->dup_tmp_units, ctx->dup_tmp_gen))) return rc;
+    return rc_trust_commit(ctx, &ctx->trust_tmp);
 }
 
 int rc_correct_device(rc_ctx *ctx, const rc_device_batch *b)
@@ -431,7 +436,8 @@ static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t)
     }
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if ((rc = rc_recount_take(ctx, d_seq, nbytes))) return rc;  // (rc_recount_follow: the traced entry point's batches complete here)
-    return rc_dups_commit(ctx, &ctx->dup_tmp, &ctx->dup_tmp_units, ctx->dup_tmp_gen);  // (the duplicate census: likewise)
+    if ((rc = rc_dups_commit(ctx, &ctx->dup_tmp, &ctx->dup_tmp_units, ctx->dup_tmp_gen))) return rc;  // (the duplicate census: likewise)
+    return rc_trust_commit(ctx, &ctx->trust_tmp);                                                      // (the trust profile too)
 }
 
 }  // extern "C"

@@ -84,6 +84,8 @@ struct rc_slot {
     rc_dbuf d_dup;
     size_t dup_units = 0;
     uint64_t dup_gen = 0;
+    // trust profile: the counts of the batch in flight, before | after, until its wait accepts it
+    rc_trust_staged trust;
     uint32_t fix_room = 0;
     bool fix_pinned = false;
 };
@@ -158,4 +160,11 @@ void rc_report_release(rc_ctx *ctx);
 int rc_dups_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_dbuf *keys, size_t *units, uint64_t *gen);
 int rc_dups_commit(rc_ctx *ctx, const rc_dbuf *keys, size_t *units, uint64_t gen);
 void rc_dups_release(rc_ctx *ctx);
+// rc_api_trust.hip -- the trust profile by read position, hooked in where the duplicate census is: stage (version 0 in front
+// of the first correction kernel: zeroes st's two rc_trust_counts and counts the arena as it is into the first; version 1
+// behind the last one: into the second), both on ctx's stream; commit: a completed batch's staged counts added to the profile
+// of the context the batch was submitted to, complete on return.  All do nothing while no profile is open.
+int rc_trust_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_trust_staged *st);
+int rc_trust_commit(rc_ctx *ctx, rc_trust_staged *st);
+void rc_trust_release(rc_ctx *ctx);
 }

@@ -40,6 +40,7 @@ static int slot_acquire(rc_ctx_full *ctx, int slot, const char *name, const char
     }
     sl.weak_out = nullptr;  // (slot_download sets it for a batch that has a weak-profile registration)
     sl.dup_units = 0;       // (rc_dups_stage sets it for a batch that a duplicate census is open for)
+    sl.trust.staged = false;  // (rc_trust_stage: likewise, for a trust profile)
     *out = &sl;
     return RC_OK;
 }
@@ -196,6 +197,7 @@ static int slot_wait_fix_list(rc_ctx_full *ctx, rc_slot &sl, const char *name)
     // rc_recount_follow: before the slot can be reused (a batch that did not fit its fix list comes again and is taken then)
     if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;
     if (const int frc = rc_dups_commit(ctx, &sl.d_dup, &sl.dup_units, sl.dup_gen)) return frc;  // the duplicate census: likewise
+    if (const int frc = rc_trust_commit(ctx, &sl.trust)) return frc;  // the trust profile: likewise
     if (sl.rep_staged) {  // the correction report: this submission is the one that counts
         sl.rep_staged = false;
         if (const int frc = rc_report_commit(ctx, &sl.d_rep)) return frc;
@@ -295,8 +297,10 @@ static int submit_bytes(rc_ctx_full *ctx, const rc_batch *b, int slot)
     const uint32_t qsplit = qbits && b->mode == 1 ? (uint32_t)sl.bytes1 : 0xFFFFFFFFu;
     // (the duplicate census: the keys of the bases as uploaded, and behind the last kernel those of the bases as corrected)
     if ((rc = rc_dups_stage(ctx, &db, 0, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
+    if ((rc = rc_trust_stage(ctx, &db, 0, &sl.trust))) return rc;  // (the trust profile: the same two places)
     if ((rc = rc_correct_device_impl(ctx, &db, qsplit, (uint32_t)qbase2))) return rc;
     if ((rc = rc_dups_stage(ctx, &db, 1, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
+    if ((rc = rc_trust_stage(ctx, &db, 1, &sl.trust))) return rc;
     // (the correction report: no second submission on this path -- counted here, before the event rc_wait waits for)
     if ((rc = rc_report_count(ctx, &db, qsplit, (uint32_t)qbase2, -1, nullptr, nullptr))) return rc;
     // the corrected arena, then the results: always to the caller's four arrays one by one
@@ -329,6 +333,7 @@ static int wait_bytes(rc_ctx_full *ctx, int slot)
     RC_CHECK_HIP(ctx, hipEventSynchronize(sl.e_done));
     if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;  // (rc_recount_follow: before the slot can be reused)
     if (const int frc = rc_dups_commit(ctx, &sl.d_dup, &sl.dup_units, sl.dup_gen)) return frc;  // (the duplicate census: likewise)
+    if (const int frc = rc_trust_commit(ctx, &sl.trust)) return frc;  // (the trust profile: likewise)
     if (!sl.seq_pinned) {
         memcpy(sl.b.seq, sl.p_seq.p, sl.bytes1);
         if (sl.b.mode == 1) memcpy(sl.b.seq2, (char *)sl.p_seq.p + sl.bytes1, sl.bytes2);
@@ -433,8 +438,10 @@ static int submit_packed(rc_ctx_full *ctx, rc_packed_batch *b, int slot)
                                                     (int32_t *)sl.d_res.p);
     // (the duplicate census: the keys of the bases as they arrived, and behind the last kernel those of the bases as corrected)
     if ((rc = rc_dups_stage(ctx, &db, 0, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
+    if ((rc = rc_trust_stage(ctx, &db, 0, &sl.trust))) return rc;  // (the trust profile: the same two places)
     if ((rc = rc_correct_device_impl(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0))) return rc;
     if ((rc = rc_dups_stage(ctx, &db, 1, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
+    if ((rc = rc_trust_stage(ctx, &db, 1, &sl.trust))) return rc;
     // (the correction report: staged, the wait decides whether this submission is the one that counts)
     if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0, &sl.d_rep, &sl.rep_staged))) return rc;
     uint32_t *d_fix_pos, *d_nfix = (uint32_t *)sl.d_fix.p;
@@ -531,8 +538,10 @@ static int submit_resident(rc_ctx_full *ctx, rc_resident_batch *b, int slot)
                                                     (int32_t *)sl.d_res.p);
     // (the duplicate census: the keys of the bases as they arrived, and behind the last kernel those of the bases as corrected)
     if ((rc = rc_dups_stage(ctx, &db, 0, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
+    if ((rc = rc_trust_stage(ctx, &db, 0, &sl.trust))) return rc;  // (the trust profile: the same two places)
     if ((rc = rc_correct_device_impl(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0))) return rc;
     if ((rc = rc_dups_stage(ctx, &db, 1, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
+    if ((rc = rc_trust_stage(ctx, &db, 1, &sl.trust))) return rc;
     // (the correction report: staged, the wait decides whether this submission is the one that counts)
     if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0, &sl.d_rep, &sl.rep_staged))) return rc;
     uint32_t *d_fix_pos, *d_nfix = (uint32_t *)sl.d_fix.p;

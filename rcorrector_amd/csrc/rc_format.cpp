@@ -166,6 +166,47 @@ bool write_dup_census(const char *path, const rc_dup_census &D, uint32_t max_bin
     return fclose(fp) == 0 && ok;
 }
 
+void add_trust_profile(rc_trust_profile &to, const rc_trust_profile &from)
+{
+    to.reads[0] += from.reads[0];
+    to.reads[1] += from.reads[1];
+    static_assert(sizeof(rc_trust_counts) % 8 == 0, "64-bit counts throughout");
+    uint64_t *t = (uint64_t *)&to.before;
+    const uint64_t *f = (const uint64_t *)&from.before;
+    for (size_t i = 0; i < 2 * sizeof(rc_trust_counts) / 8; ++i) t[i] += f[i];  // (before | after)
+}
+
+bool write_trust_profile(const char *path, const rc_trust_profile &T, bool two_mates)
+{
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return false;
+    typedef unsigned long long ull;
+    const int mates = two_mates ? 2 : 1;
+    bool ok = fprintf(fp, "k\t%d\nmin_count\t%d\n", T.k, T.min_count) > 0;
+    for (int m = 0; m < mates; ++m) ok = ok && fprintf(fp, "reads\t%d\t%llu\n", m + 1, (ull)T.reads[m]) > 0;
+    const rc_trust_counts *ver[2] = {&T.before, &T.after};
+    const char *name[2] = {"before", "after"};
+    for (int v = 0; v < 2; ++v)
+        for (int m = 0; m < mates; ++m) {
+            ull w = 0, s = 0, k = 0;
+            for (int p = 0; p < RC_TRUST_MAX_LEN; ++p) {
+                w += ver[v]->windows[m][p];
+                s += ver[v]->solid5[m][p];
+                k += ver[v]->weak5[m][p];
+            }
+            ok = ok && fprintf(fp, "total\t%s\t%d\t%llu\t%llu\t%llu\t%llu\n", name[v], m + 1, w, s, k, w - s - k) > 0;
+        }
+    for (int end = 0; end < 2; ++end)
+        for (int v = 0; v < 2; ++v)
+            for (int m = 0; m < mates; ++m)
+                for (int p = 0; p < RC_TRUST_MAX_LEN && ok; ++p) {
+                    const ull w = ver[v]->windows[m][p], s = end ? ver[v]->solid3[m][p] : ver[v]->solid5[m][p],
+                              k = end ? ver[v]->weak3[m][p] : ver[v]->weak5[m][p];
+                    if (w) ok = fprintf(fp, "%s\t%s\t%d\t%d\t%llu\t%llu\t%llu\t%llu\n", end ? "pos3" : "pos5", name[v], m + 1, p, w, s, k, w - s - k) > 0;
+                }
+    return fclose(fp) == 0 && ok;
+}
+
 bool write_change_report(const char *path, const rc_change_report &R, bool two_mates)
 {
     FILE *fp = fopen(path, "wb");

@@ -179,6 +179,12 @@ bool write_change_report(const char *path, const rc_change_report &R, bool two_m
 // before <n> / distinct after <n> / copies <c> <distinct before> <distinct after>, a line per c where either is non-zero (the
 // line of c = max_bin: that many copies or more)
 bool write_dup_census(const char *path, const rc_dup_census &D, uint32_t max_bin, const char *unit);
+// the trust profile by read position (rcorrector_amd.h: rc_trust_profile) as tab-separated text: k <k> / min_count <n> / reads
+// <mate 1|2> <n> / total <before|after> <mate> <windows> <solid> <weak> <invalid> / pos5 and pos3 <before|after> <mate> <p>
+// <windows> <solid> <weak> <invalid>, a line per position p that some read has a window at; mate 2 only with two_mates.
+// add_trust_profile: to += from, every count (what several GPUs' profiles become one with)
+bool write_trust_profile(const char *path, const rc_trust_profile &T, bool two_mates);
+void add_trust_profile(rc_trust_profile &to, const rc_trust_profile &from);
 // GetBadQuality's two histograms over the records of one block (main.cpp:88-128), at most `room` of them
 void quality_histograms(const Block &b, int lpr, size_t room, std::vector<int32_t> &fh, std::vector<int32_t> &lh, int *total);
 

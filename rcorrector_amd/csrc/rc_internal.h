@@ -69,12 +69,23 @@ struct rc_arena_set {
 
 #define RC_MAX_SLOTS 4
 
+// trust profile: the counts of one batch in flight, an rc_trust_counts of its bases as they arrived and one of its bases as
+// corrected, until the batch completes (staged == false: none were taken); gen: the profile they were taken for
+struct rc_trust_staged {
+    rc_dbuf buf;
+    bool staged = false;
+    uint64_t gen = 0;
+    uint32_t n_reads = 0;
+    int mode = 0, max_read_len = 0;
+    int32_t min_count = 1;
+};
+
 struct rc_kernel_timer {
     double ms = 0;       // accumulated
     uint64_t launches = 0;
 };
 
-enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_COUNT };
+enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_TRUST_PLANES = 5, RC_T_TRUST = 6, RC_T_COUNT };
 
 struct rc_ctx {
     int device = 0;
@@ -178,6 +189,18 @@ struct rc_ctx {
     rc_dbuf dup_tmp;
     size_t dup_tmp_units = 0;
     uint64_t dup_tmp_gen = 0;
+    // trust profile (rc_trust_profile_begin; kernels in rc_trust.hip).  In the context it was opened on (the batches of its slot
+    // lanes add to it too: lane_parent): trust_acc, two rc_trust_counts in HBM (before | after), the reads seen per mate, the
+    // threshold, and trust_gen, which counts the begins; the lanes' waits add under dup_mutex.  In the context a batch or
+    // rc_trust_profile_device RUNS in: the bit planes and the wavefronts' partial counts of the arena profiled last (scratch,
+    // serialised on its compute stream), and trust_tmp, the staged counts of the batch of an entry point that has no slot
+    std::atomic<bool> trust_open{false};  // (read by the lanes' submits without the mutex)
+    void *trust_acc = nullptr;
+    uint64_t trust_reads[2] = {0, 0};
+    int32_t trust_min = 1;
+    uint64_t trust_gen = 0;
+    rc_dbuf trust_planes, trust_part;
+    rc_trust_staged trust_tmp;
 
     // batch scratch
     rc_dbuf counts;   // int32 per arena byte
@@ -312,6 +335,16 @@ int rc_launch_report_commit(rc_ctx *ctx, const unsigned long long *d_staged, uns
 // rc_weak.hip: solid / weak bit planes of the arena into `planes` (grow-only), then d_out[r] = the rc_read_weak of read r
 int rc_launch_weak_profile(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int min_count, rc_dbuf *planes,
                            void *d_out);
+
+// rc_weak.hip: the two bit planes alone (what rc_launch_weak_profile launches first): *solid / *weak point into `planes`,
+// *lead = the bytes between the 16-byte boundary the planes start at and d_seq.  rc_trust.hip: the planes of the arena at
+// min_count into `planes`, every wavefront's counts into `partials` (both grow-only), their column sums added to d_counts
+// (an rc_trust_counts in HBM); max_read_len picks the instance.  rc_launch_trust_add: d_dst[i] += d_src[i], n_words uint64
+int rc_launch_weak_planes(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int min_count, rc_dbuf *planes, const uint64_t **solid_out,
+                          const uint64_t **weak_out, uint32_t *lead_out);
+int rc_launch_trust_profile(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int max_read_len, int mode,
+                            int min_count, rc_dbuf *planes, rc_dbuf *partials, void *d_counts);
+int rc_launch_trust_add(rc_ctx *ctx, const void *d_src, void *d_dst, uint32_t n_words);
 
 // rc_dups.hip: one 128-bit key per unit of an arena (mode as rc_device_batch: n_reads units, or n_reads / 2 pairs) on stream st;
 // the census of n keys in HBM (left as they are) into host arrays copies[max_bin + 1], *distinct -- synchronous

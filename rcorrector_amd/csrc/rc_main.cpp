@@ -29,6 +29,9 @@
 // weak-k-mer profile of the corrected reads (rcorrector_amd.h: rc_read_weak; -weak-min: the count below which a k-mer is weak).
 // -dups FILE writes the duplicate census (rcorrector_amd.h: rc_dup_census; rc_format.h: write_dup_census): how many reads or
 // pairs are exact copies of one another, as uploaded and as corrected, from 128-bit keys taken on the GPU as the batches complete.
+// -trust-by-pos FILE writes the k-mer trust profile by read position (rcorrector_amd.h: rc_trust_profile; rc_format.h:
+// write_trust_profile): the reads with a solid / weak k-mer window at every position from either end, per mate, as uploaded and
+// as corrected, counted on the GPU as the batches complete (-weak-min: the count below which a k-mer is weak).
 #include <fcntl.h>
 #include <malloc.h>
 #include <sys/stat.h>
@@ -76,7 +79,7 @@ static void print_help()
             "\t\tread in front of its first / behind its last k-mer that the table holds (unfixable reads keep their mark and get no tag);\n"
             "\t\tnothing is trimmed; one more line on stderr counts the reads with a bad prefix, a bad suffix, and no such k-mer at all\n"
             "\t\t(every read counts there, unfixable ones included); not with -verbose\n"
-            "\t-weak-min INT: with -weak-ends, a k-mer counted fewer times than this in the table is weak (default: 1)\n"
+            "\t-weak-min INT: with -weak-ends and -trust-by-pos, a k-mer counted fewer times than this in the table is weak (default: 1)\n"
             "\t-dups STRING: also write the duplicate census, tab-separated text: the units (reads, or pairs for -1/-2 and -i input), the\n"
             "\t\tdistinct units before and after correction, and for every number of copies c the distinct units that occur c times,\n"
             "\t\tbefore and after; two units are copies when their bases are byte for byte equal (mate 1 with mate 1, mate 2 with\n"
@@ -84,6 +87,11 @@ static void print_help()
             "\t\tin GPU memory until the end of the run, at most 2^32 - 1 units; with -gpus above 1 the GPUs' keys are merged on the\n"
             "\t\tfirst; the input is all single-end or all paired (-p / -i), not a mix; not with -verbose\n"
             "\t-dups-max INT: with -dups, units with this many copies or more are counted in the last line (default: 10000)\n"
+            "\t-trust-by-pos STRING: also write the k-mer trust profile by read position, tab-separated text: for every k-mer window\n"
+            "\t\tposition counted from the 5' end (pos5) and from the 3' end (pos3, 0 = the last window), per mate, before and after\n"
+            "\t\tcorrection: the reads that have a window there and those whose window is solid (in the table at least -weak-min\n"
+            "\t\ttimes), weak, or invalid (holds a letter outside ACGT); one more line on stderr gives the weak share of the valid\n"
+            "\t\twindows before and after; with -gpus above 1 the GPUs' counts are added up; not with -verbose\n"
             "\t-verbose-iter INT: threshold iterations recorded per read for -verbose (default: 64)\n");
 }
 
@@ -96,7 +104,7 @@ int main(int argc, char **argv)
     std::vector<ReadFile> &files = run.files, &mates = run.mates;
     int max_fix_per_k = 4, i;
     double wk = 0.95;
-    const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr, *report = nullptr, *dups = nullptr;
+    const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr, *report = nullptr, *dups = nullptr, *trust = nullptr;
     long dups_max = 10000;
     long histo_max = 10000;
     std::string od = "./";
@@ -159,6 +167,8 @@ int main(int argc, char **argv)
             dups = argv[++i];
         else if (!strcmp("-dups-max", argv[i]))
             dups_max = atol(argv[++i]);
+        else if (!strcmp("-trust-by-pos", argv[i]))
+            trust = argv[++i];
         else if (!strcmp("-weak-ends", argv[i]))
             run.weak_ends = true;
         else if (!strcmp("-weak-min", argv[i]))
@@ -176,6 +186,7 @@ int main(int argc, char **argv)
     g_verbose = verbose;
     if (run.weak_ends && verbose) die("rcorrector: usage: -weak-ends cannot be combined with -verbose (the transcript's entry point takes no weak-k-mer profile)\n");
     if (dups && verbose) die("rcorrector: usage: -dups cannot be combined with -verbose (small batches through the transcript's entry point: run the census without it)\n");
+    if (trust && verbose) die("rcorrector: usage: -trust-by-pos cannot be combined with -verbose (small batches through the transcript's entry point: run the profile without it)\n");
     if (dups && (dups_max < 1 || dups_max > (1l << 28))) die("rcorrector: usage: -dups-max must be 1..%ld\n", 1l << 28);
     if (run.weak_min < 1) die("rcorrector: usage: -weak-min must be at least 1\n");
     if (g_trace_iter < 1) g_trace_iter = 1;
@@ -527,6 +538,11 @@ int main(int argc, char **argv)
         for (int c = 0; c < nctx; ++c)
             if (rc_dup_census_begin(ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
 
+    // -trust-by-pos: every context counts the batches that complete on it, whatever the transport
+    if (trust)
+        for (int c = 0; c < nctx; ++c)
+            if (rc_trust_profile_begin(ctx[c], run.weak_min)) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+
     // pipeline: reader (this thread) -> `inflight` workers per GPU -> writer thread (input order)
     warm.join();
     stamp("batch buffers ready");
@@ -594,6 +610,28 @@ int main(int argc, char **argv)
         fprintf(stderr, "Duplicates: %llu %s, %llu distinct before correction (duplicate fraction %.4f), %llu after (%.4f)\n", (unsigned long long)dc.units, unit,
                 (unsigned long long)dc.distinct_before, dc.units ? 1.0 - (double)dc.distinct_before / u : 0.0, (unsigned long long)dc.distinct_after,
                 dc.units ? 1.0 - (double)dc.distinct_after / u : 0.0);
+    }
+    if (trust) {  // the contexts' counts, added up
+        std::vector<rc_trust_profile> tp(2);
+        for (int c = 0; c < nctx; ++c) {
+            if (rc_trust_profile_get(ctx[c], &tp[c ? 1 : 0])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+            if (c) add_trust_profile(tp[0], tp[1]);
+            if (rc_trust_profile_end(ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+        }
+        bool two_mates = false;
+        for (const ReadFile &f : files) two_mates = two_mates || f.paired || f.interleaved;
+        if (!write_trust_profile(trust, tp[0], two_mates)) die("rcorrector: could not write %s\n", trust);
+        uint64_t valid[2] = {0, 0}, weak[2] = {0, 0};
+        const rc_trust_counts *ver[2] = {&tp[0].before, &tp[0].after};
+        for (int v = 0; v < 2; ++v)
+            for (int m = 0; m < 2; ++m)
+                for (int p = 0; p < RC_TRUST_MAX_LEN; ++p) {
+                    weak[v] += ver[v]->weak5[m][p];
+                    valid[v] += ver[v]->weak5[m][p] + ver[v]->solid5[m][p];
+                }
+        fprintf(stderr, "Trust by position (k-mers counted below %d are weak): %llu of %llu valid k-mer windows weak before correction (%.4f), %llu of %llu after (%.4f)\n",
+                run.weak_min, (unsigned long long)weak[0], (unsigned long long)valid[0], valid[0] ? (double)weak[0] / (double)valid[0] : 0.0,
+                (unsigned long long)weak[1], (unsigned long long)valid[1], valid[1] ? (double)weak[1] / (double)valid[1] : 0.0);
     }
     if (histo_after) {
         const double th0 = now_s();

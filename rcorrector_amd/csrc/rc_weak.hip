@@ -101,6 +101,29 @@ __global__ __launch_bounds__(256) void k_weak_reduce(const uint64_t *__restrict_
     out[r] = rc_weak_reduce(solid, weak, (uint64_t)g0 + lead, L, k);
 }
 
+int rc_launch_weak_planes(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int min_count, rc_dbuf *planes, const uint64_t **solid_out,
+                          const uint64_t **weak_out, uint32_t *lead_out)
+{
+    const uint32_t lead = (uint32_t)((uintptr_t)d_seq & 15u);
+    const size_t span = (size_t)lead + nbytes;
+    const unsigned G = (unsigned)((span + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
+    const size_t plane_words = (size_t)(G ? G : 1) * (RC_PROBE_TILE / 64);
+    if (const int rc = rc_dbuf_reserve(ctx, planes, plane_words * 16)) return rc;
+    uint64_t *solid = (uint64_t *)planes->p, *weak = solid + plane_words;
+    if (G) {
+        if (ctx->ext)
+            hipLaunchKernelGGL(k_weak_planes<true>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq - lead, lead, nbytes, ctx->k,
+                               min_count, solid, weak);
+        else
+            hipLaunchKernelGGL(k_weak_planes<false>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq - lead, lead, nbytes, ctx->k,
+                               min_count, solid, weak);
+    }
+    *solid_out = solid;
+    *weak_out = weak;
+    *lead_out = lead;
+    return RC_OK;
+}
+
 int rc_launch_weak_profile(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int min_count, rc_dbuf *planes,
                            void *d_out)
 {
@@ -110,21 +133,10 @@ int rc_launch_weak_profile(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, con
         return RC_ERR_STATE;
     }
     static_assert(sizeof(rc_weak_vals) == 16, "rc_read_weak");
-    const uint32_t lead = (uint32_t)((uintptr_t)d_seq & 15u);
-    const size_t span = (size_t)lead + nbytes;
-    const unsigned G = (unsigned)((span + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
-    const size_t plane_words = (size_t)(G ? G : 1) * (RC_PROBE_TILE / 64);
-    if (const int rc = rc_dbuf_reserve(ctx, planes, plane_words * 16)) return rc;
-    uint64_t *solid = (uint64_t *)planes->p, *weak = solid + plane_words;
+    const uint64_t *solid, *weak;
+    uint32_t lead;
     rc_timer_begin(ctx);
-    if (G) {
-        if (ctx->ext)
-            hipLaunchKernelGGL(k_weak_planes<true>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq - lead, lead, nbytes, ctx->k,
-                               min_count, solid, weak);
-        else
-            hipLaunchKernelGGL(k_weak_planes<false>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq - lead, lead, nbytes, ctx->k,
-                               min_count, solid, weak);
-    }
+    if (const int rc = rc_launch_weak_planes(ctx, d_seq, nbytes, min_count, planes, &solid, &weak, &lead)) return rc;
     hipLaunchKernelGGL(k_weak_reduce, dim3((n_reads + 255) / 256), dim3(256), 0, ctx->stream, solid, weak, lead, nbytes, d_off, n_reads, ctx->k,
                        (rc_weak_vals *)d_out);
     rc_timer_end(ctx, RC_T_WEAK);
