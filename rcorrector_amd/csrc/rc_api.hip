@@ -35,9 +35,9 @@ void rc_table_release(rc_ctx *ctx)
     // a slot lane may still be probing the table it borrowed (streams of its own): wait for it and take the loan back before
     // the buckets go -- the next batch of that slot gets the new table with its refresh (rc_slot_lane)
     if (ctx->d_buckets && !ctx->buckets_borrowed) {
+        (void)rc_drain(ctx);
         for (rc_ctx *ln : ctx->lane) {
             if (!ln || ln->d_buckets != ctx->d_buckets) continue;
-            (void)hipStreamSynchronize(ln->stream);
             ln->d_buckets = nullptr;
             ln->buckets_borrowed = false;
             ln->n_entries = 0;
@@ -52,6 +52,15 @@ void rc_table_release(rc_ctx *ctx)
     ctx->filter_words = 0;
     ctx->table_bytes = 0;
     ctx->n_entries = 0;
+}
+
+int rc_drain(rc_ctx *ctx)
+{
+    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (rc_ctx *ln : ctx->lane)
+        if (ln) RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream));
+    return RC_OK;
 }
 
 rc_table_view rc_view(const rc_ctx *ctx)
@@ -239,7 +248,7 @@ void rc_destroy(rc_ctx *c)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     rc_dbuf *bufs[] = {&ctx->counts, &ctx->strong, &ctx->info, &ctx->stack, &ctx->work,
                        &ctx->h_seq, &ctx->h_qual, &ctx->h_off, &ctx->h_res, &ctx->trace, &ctx->cls, &ctx->worklist, &ctx->sel_tmp,
-                       &ctx->loc_a, &ctx->loc_list, &ctx->loc_span, &ctx->tier_flag, &ctx->tier_list, &ctx->cand, &ctx->single_list, &ctx->runs, &ctx->bs_dev, &ctx->weak_planes, &ctx->dup_tmp, &ctx->trust_planes, &ctx->trust_part, &ctx->trust_tmp.buf};
+                       &ctx->loc_a, &ctx->loc_list, &ctx->loc_span, &ctx->tier_flag, &ctx->tier_list, &ctx->cand, &ctx->single_list, &ctx->runs, &ctx->bs_dev, &ctx->weak_planes, &ctx->trust_planes, &ctx->trust_part};
     for (rc_dbuf *b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (ctx->slots) {
@@ -249,15 +258,16 @@ void rc_destroy(rc_ctx *c)
             rc_hbuf *hb[] = {&sl.p_seq, &sl.p_qual, &sl.p_off, &sl.p_res, &sl.p_in, &sl.p_fix, &sl.p_nfix, &sl.p_weak};
             for (rc_hbuf *h : hb)
                 if (h->p) (void)hipHostFree(h->p);
-            rc_dbuf *db[] = {&sl.d_seq, &sl.d_qual, &sl.d_off, &sl.d_res, &sl.d_packed, &sl.d_exc, &sl.d_fix, &sl.d_rep, &sl.d_weak, &sl.d_dup, &sl.trust.buf};
+            rc_dbuf *db[] = {&sl.d_seq, &sl.d_qual, &sl.d_off, &sl.d_res, &sl.d_packed, &sl.d_exc, &sl.d_fix, &sl.d_weak};
             for (rc_dbuf *d : db)
                 if (d->p) (void)hipFree(d->p);
             hipEvent_t ev[] = {sl.e_h2d, sl.e_k, sl.e_done};
             for (hipEvent_t e : ev)
                 if (e) (void)hipEventDestroy(e);
         }
-        delete[] ctx->slots;
     }
+    rc_observed_drop_all(ctx, RC_OBS_ALL, true);  // (what the batch observers staged, here and in the slots; the lanes are gone)
+    delete[] ctx->slots;
     if (ctx->s_h2d) (void)hipStreamDestroy(ctx->s_h2d);
     if (ctx->s_d2h) (void)hipStreamDestroy(ctx->s_d2h);
     ctx->cnt.release();

@@ -13,43 +13,18 @@ int rc_probe_device(rc_ctx *ctx, const uint8_t *d_seq, uint64_t nbytes, int32_t 
 }
 
 
-// (the correction report: rc_correct_device has no wait -- the batch counts at the end of the call, in stream order)
-// (the duplicate census: the batch's keys go to scratch of the context; `commit`: into the census at the end of the call,
-// which then returns when they are in -- rc_correct_batch_traced commits where its batch completes instead; the trust
-// profile's counts take the same way, through the context's trust_tmp)
-static int correct_device_census(rc_ctx *ctx, const rc_device_batch *b, bool commit)
-{
-    if (!ctx || !b) return RC_ERR_ARG;
-    const bool keyed = ctx->dup_open && b->n_reads && b->mode >= 0 && b->mode <= 2 && b->d_seq && b->d_off && b->nbytes < (1ull << 32) &&
-                       !(b->mode != 0 && (b->n_reads & 1u));  // (what rc_correct_device_impl refuses is refused there, unkeyed)
-    int rc;
-    ctx->dup_tmp_units = 0;
-    if (keyed) {
-        RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-        if ((rc = rc_dups_stage(ctx, b, 0, &ctx->dup_tmp, &ctx->dup_tmp_units, &ctx->dup_tmp_gen))) return rc;
-    }
-    if ((rc = rc_trust_stage(ctx, b, 0, &ctx->trust_tmp))) return rc;
-    if ((rc = rc_correct_device_impl(ctx, b, 0xFFFFFFFFu, 0))) return rc;
-    if ((rc = rc_report_count(ctx, b, 0xFFFFFFFFu, 0, -1, nullptr, nullptr))) return rc;
-    if (keyed && (rc = rc_dups_stage(ctx, b, 1, &ctx->dup_tmp, &ctx->dup_tmp_units, &ctx->dup_tmp_gen))) return rc;
-    if ((rc = rc_trust_stage(ctx, b, 1, &ctx->trust_tmp))) return rc;
-    if (!commit) return RC_OK;
-    if ((rc = rc_dups_commit(ctx, &ctx->dup_tmp, &ctx->dup_tmp_units, ctx->dup_tmp_gen))) return rc;
-    return rc_trust_commit(ctx, &ctx->trust_tmp);
-}
-
+// rc_correct_device has no wait: the batch is observed and completes within the call (rc_api_observe.hip), which returns when
+// the census and the profile have it; the report counts at the end of the call, in stream order
 int rc_correct_device(rc_ctx *ctx, const rc_device_batch *b)
 {
-    return correct_device_census(ctx, b, true);
+    if (!ctx || !b) return RC_ERR_ARG;
+    if (const int rc = rc_correct_observed(ctx, b, 0xFFFFFFFFu, 0, -1, &ctx->obs, false)) return rc;
+    return rc_batch_completed(ctx, &ctx->obs, nullptr, 0);
 }
 
-// qual_split / qual_base2 (quality-bit mode only): arena bytes from qual_split on have their bits at
-// byte qual_base2 of d_qual -- the second arena of a paired host batch, whose bit array is separate
-// qual_bits: -1 = as rc_set_quality_bits says, 0 / 1 = this batch's quality arena holds bytes / bits (the packed boundary)
-int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits)
+// what no correction entry point accepts of a batch descriptor with reads in it, refused before anything is launched
+int rc_correct_check(rc_ctx *ctx, const rc_device_batch *b)
 {
-    if (!ctx || !b) return RC_ERR_ARG;
-    if (b->n_reads == 0) return RC_OK;
     if (b->mode < 0 || b->mode > 2 || !b->d_seq || !b->d_qual || !b->d_off || !b->d_ret || !b->d_l || !b->d_m || !b->d_h) {
         rc_set_error(ctx, "correct_device: bad batch descriptor");
         return RC_ERR_ARG;
@@ -68,10 +43,16 @@ int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_
         rc_set_error(ctx, "correct: %s mode needs an even number of reads (got %u)", b->mode == 1 ? "paired" : "interleaved", b->n_reads);
         return RC_ERR_ARG;
     }
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return RC_OK;
+}
+
+// the correction kernels over a batch rc_correct_check has accepted, ctx's device current (rc_correct_observed)
+// qual_split / qual_base2 (quality-bit mode only): arena bytes from qual_split on have their bits at
+// byte qual_base2 of d_qual -- the second arena of a paired host batch, whose bit array is separate
+// qual_bits: -1 = as rc_set_quality_bits says, 0 / 1 = this batch's quality arena holds bytes / bits (the packed boundary)
+int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits)
+{
     int rc;
-    // the correction report, if one is armed: the arena as it is now (the entry point counts the batch against it, once)
-    if ((rc = rc_report_snapshot(ctx, b->d_seq, (size_t)b->nbytes))) return rc;
     bool fused = false;  // probe and threshold kernels ran as one
     if ((rc = rc_dbuf_reserve(ctx, &ctx->counts, (size_t)b->nbytes * 4 + 256))) return rc;
     if ((rc = rc_dbuf_reserve(ctx, &ctx->strong, (size_t)b->n_reads * 4 + 256))) return rc;
@@ -299,7 +280,8 @@ int rc_correct_read(rc_ctx *ctx, char *seq, const char *qual, int32_t pair_stron
     int rc = one_read_upload(ctx, seq, qual, a, &n1);
     if (rc) return rc;
     a.pair_override = pair_strong_threshold;
-    if ((rc = rc_report_snapshot(ctx, a.seq, n1))) return rc;
+    const uint8_t *snap;  // (the correction report alone: one read is no batch of the run for the other observers)
+    if ((rc = rc_report_snapshot(ctx, a.seq, n1, &snap))) return rc;
     if ((rc = rc_launch_probe(ctx, a.seq, n1, (int32_t *)ctx->counts.p))) return rc;
     // no threshold kernel, no classification: k_correct computes the read's own threshold (its single-end front end) and
     // takes the pair's from the argument, exactly the reference's call
@@ -309,7 +291,7 @@ int rc_correct_read(rc_ctx *ctx, char *seq, const char *qual, int32_t pair_stron
     if ((rc = rc_launch_correct(ctx, a))) return rc;
     if ((rc = rc_launch_summary(ctx, a.ret, 1))) return rc;
     const rc_device_batch db = rc_device_batch_over(0, 1, n1, a.max_len, a.seq, a.qual, a.off, a.ret);  // (one_read_upload: a.ret | l | m | h is one block)
-    if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, 0, nullptr, nullptr))) return rc;
+    if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, 0, snap, nullptr))) return rc;
     RC_CHECK_HIP(ctx, hipMemcpyAsync(seq, a.seq, n1 - 1, hipMemcpyDeviceToHost, ctx->stream));
     RC_CHECK_HIP(ctx, hipMemcpyAsync(ret, a.ret, 4, hipMemcpyDeviceToHost, ctx->stream));
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -336,11 +318,7 @@ int rc_kmer_info_read(rc_ctx *ctx, const char *seq, int32_t *l, int32_t *m, int3
 
 int rc_sync(rc_ctx *ctx)
 {
-    if (!ctx) return RC_ERR_ARG;
-    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (rc_ctx *ln : ctx->lane)
-        if (ln) RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream));
-    return RC_OK;
+    return ctx ? rc_drain(ctx) : (int)RC_ERR_ARG;
 }
 
 static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t);
@@ -411,7 +389,7 @@ static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t)
     }
     RC_CHECK_HIP(ctx, hipMemcpyAsync(ctx->h_off.p, off.data(), (total_reads + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     const rc_device_batch db = rc_device_batch_over(b->mode, total_reads, nbytes, max_len, d_seq, d_qual, (const uint32_t *)ctx->h_off.p, (int32_t *)ctx->h_res.p);
-    if ((rc = correct_device_census(ctx, &db, false))) return rc;
+    if ((rc = rc_correct_observed(ctx, &db, 0xFFFFFFFFu, 0, -1, &ctx->obs, false))) return rc;
     RC_CHECK_HIP(ctx, hipMemcpyAsync(b->seq, d_seq, bytes1, hipMemcpyDeviceToHost, ctx->stream));
     if (b->mode == 1) RC_CHECK_HIP(ctx, hipMemcpyAsync(b->seq2, d_seq + bytes1, bytes2, hipMemcpyDeviceToHost, ctx->stream));
     RC_CHECK_HIP(ctx, hipMemcpyAsync(b->ret, db.d_ret, total_reads * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -435,9 +413,7 @@ static int correct_batch_impl(rc_ctx *c, rc_batch *b, rc_trace *t)
         }
     }
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = rc_recount_take(ctx, d_seq, nbytes))) return rc;  // (rc_recount_follow: the traced entry point's batches complete here)
-    if ((rc = rc_dups_commit(ctx, &ctx->dup_tmp, &ctx->dup_tmp_units, ctx->dup_tmp_gen))) return rc;  // (the duplicate census: likewise)
-    return rc_trust_commit(ctx, &ctx->trust_tmp);                                                      // (the trust profile too)
+    return rc_batch_completed(ctx, &ctx->obs, d_seq, nbytes);  // (the traced entry point's batches complete here)
 }
 
 }  // extern "C"

@@ -3,9 +3,10 @@
 //
 // Where the keys go: a batch's BEFORE keys are taken on the stream of the context it runs in once its bases are in HBM and
 // before the first correction kernel, its AFTER keys behind the last one (rc_dups_stage), both into scratch of the slot (or of
-// the context, for the entry points that have no slot).  They reach the census when the batch completes (rc_dups_commit,
-// where rc_recount_take sits) -- once, however often a batch that did not fit its fix list was submitted.  Slot lanes are
-// contexts on streams of their own: they append to the census of the context they serve under its dup_mutex.  A commit is
+// the context, for the entry points that have no slot).  They reach the census when the batch completes (rc_dups_commit)
+// -- once, however often a batch that did not fit its fix list was submitted.  Both steps are called from one place each,
+// rc_correct_observed and rc_batch_completed (rc_api_observe.hip), which say where they sit for every entry point.  Slot lanes
+// are contexts on streams of their own: they append to the census of the context they serve under its obs_mutex.  A commit is
 // complete on return, so the accumulators can be moved when they grow; a growth that fails fails the call that completes the
 // batch with RC_STATUS_NOSPACE.
 #include "rc_api_internal.h"
@@ -14,27 +15,25 @@
 
 extern "C" {
 
-static rc_ctx *dups_home(rc_ctx *ctx) { return ctx->is_lane && ctx->lane_parent ? ctx->lane_parent : ctx; }
-
-int rc_dups_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_dbuf *keys, size_t *units, uint64_t *gen)
+int rc_dups_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_batch_observed *o)
 {
-    rc_ctx *home = dups_home(ctx);
+    rc_ctx *home = rc_home(ctx);
     if (version == 0) {
-        *units = 0;
+        o->dup_units = 0;
         if (!home->dup_open) return RC_OK;
         const size_t n = b->mode == 0 ? b->n_reads : b->n_reads >> 1;
         if (!n) return RC_OK;
-        if (const int rc = rc_dbuf_reserve(ctx, keys, 2 * n * 16)) return rc;
-        if (const int rc = rc_launch_read_keys(ctx, ctx->stream, b->d_seq, (size_t)b->nbytes, b->d_off, b->n_reads, b->mode, (uint64_t *)keys->p)) return rc;
-        *units = n;
-        *gen = home->dup_gen;
+        if (const int rc = rc_dbuf_reserve(ctx, &o->dup_keys, 2 * n * 16)) return rc;
+        if (const int rc = rc_launch_read_keys(ctx, ctx->stream, b->d_seq, (size_t)b->nbytes, b->d_off, b->n_reads, b->mode, (uint64_t *)o->dup_keys.p)) return rc;
+        o->dup_units = n;
+        o->dup_gen = home->dup_gen;
         return RC_OK;
     }
-    if (!*units) return RC_OK;  // (no census was open when the batch's bases arrived: it is in none)
-    return rc_launch_read_keys(ctx, ctx->stream, b->d_seq, (size_t)b->nbytes, b->d_off, b->n_reads, b->mode, (uint64_t *)keys->p + 2 * *units);
+    if (!o->dup_units) return RC_OK;  // (no census was open when the batch's bases arrived: it is in none)
+    return rc_launch_read_keys(ctx, ctx->stream, b->d_seq, (size_t)b->nbytes, b->d_off, b->n_reads, b->mode, (uint64_t *)o->dup_keys.p + 2 * o->dup_units);
 }
 
-// room for `more` units behind home's dup_n; called with dup_mutex held and nothing outstanding on the accumulators
+// room for `more` units behind home's dup_n; called with obs_mutex held and nothing outstanding on the accumulators
 static int dups_grow(rc_ctx *err_ctx, rc_ctx *home, size_t more)
 {
     const size_t need = home->dup_n + more;
@@ -69,18 +68,18 @@ static int dups_grow(rc_ctx *err_ctx, rc_ctx *home, size_t more)
     return RC_OK;
 }
 
-int rc_dups_commit(rc_ctx *ctx, const rc_dbuf *keys, size_t *units, uint64_t gen)
+int rc_dups_commit(rc_ctx *ctx, rc_batch_observed *o)
 {
-    const size_t n = *units;
-    *units = 0;
+    const size_t n = o->dup_units;
+    o->dup_units = 0;
     if (!n) return RC_OK;
-    rc_ctx *home = dups_home(ctx);
+    rc_ctx *home = rc_home(ctx);
     int rc = RC_OK;
     {
-        std::lock_guard<std::mutex> lk(home->dup_mutex);
-        if (!home->dup_open || home->dup_gen != gen) return RC_OK;  // (staged for a census that has ended)
+        std::lock_guard<std::mutex> lk(home->obs_mutex);
+        if (!home->dup_open || home->dup_gen != o->dup_gen) return RC_OK;  // (staged for a census that has ended)
         if (!(rc = dups_grow(ctx, home, n))) {
-            const char *src = (const char *)keys->p;
+            const char *src = (const char *)o->dup_keys.p;
             hipError_t e = hipMemcpyAsync((char *)home->dup_acc[0] + home->dup_n * 16, src, n * 16, hipMemcpyDeviceToDevice, ctx->stream);
             if (e == hipSuccess) e = hipMemcpyAsync((char *)home->dup_acc[1] + home->dup_n * 16, src + n * 16, n * 16, hipMemcpyDeviceToDevice, ctx->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -95,7 +94,7 @@ int rc_dups_commit(rc_ctx *ctx, const rc_dbuf *keys, size_t *units, uint64_t gen
     return rc;
 }
 
-void rc_dups_release(rc_ctx *ctx)
+static void dups_release(rc_ctx *ctx)
 {
     for (int v = 0; v < 2; ++v) {
         if (ctx->dup_acc[v]) (void)hipFree(ctx->dup_acc[v]);
@@ -103,36 +102,13 @@ void rc_dups_release(rc_ctx *ctx)
     }
     ctx->dup_n = ctx->dup_cap = 0;
     ctx->dup_open = false;
-    auto scratch = [](rc_ctx *c) {
-        if (!c) return;
-        if (c->dup_tmp.p) (void)hipFree(c->dup_tmp.p);
-        c->dup_tmp = rc_dbuf();
-        c->dup_tmp_units = 0;
-        if (c->slots)
-            for (int s = 0; s < RC_MAX_SLOTS; ++s) {
-                rc_slot &sl = c->slots[s];
-                if (sl.d_dup.p) (void)hipFree(sl.d_dup.p);
-                sl.d_dup = rc_dbuf();
-                sl.dup_units = 0;
-            }
-    };
-    scratch(ctx);
-    for (rc_ctx *ln : ctx->lane) scratch(ln);
-}
-
-// what ctx and its lanes have queued has run
-static int dups_drain(rc_ctx *ctx)
-{
-    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (rc_ctx *ln : ctx->lane)
-        if (ln) RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream));
-    return RC_OK;
+    rc_observed_drop_all(ctx, RC_OBS_DUPS, true);  // (the staged keys of ctx, its lanes and their slots)
 }
 
 int rc_dup_census_begin(rc_ctx *ctx)
 {
     if (!ctx) return RC_ERR_ARG;
-    std::lock_guard<std::mutex> lk(ctx->dup_mutex);
+    std::lock_guard<std::mutex> lk(ctx->obs_mutex);
     if (ctx->dup_open) {
         rc_set_error(ctx, "dup_census_begin: a census is open already (rc_dup_census_end it first)");
         return RC_ERR_STATE;
@@ -154,9 +130,8 @@ int rc_dup_census_get(rc_ctx *ctx, uint32_t max_bin, rc_dup_census *out)
         rc_set_error(ctx, "dup_census_get: max_bin must be 1..%u, out and its two arrays not NULL", RC_DUP_MAX_BIN);
         return RC_ERR_ARG;
     }
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (const int rc = dups_drain(ctx)) return rc;
-    std::lock_guard<std::mutex> lk(ctx->dup_mutex);
+    if (const int rc = rc_drain(ctx)) return rc;
+    std::lock_guard<std::mutex> lk(ctx->obs_mutex);
     out->units = ctx->dup_n;
     if (const int rc = rc_dup_census_run(ctx, (const uint64_t *)ctx->dup_acc[0], ctx->dup_n, max_bin, out->copies_before, &out->distinct_before)) return rc;
     return rc_dup_census_run(ctx, (const uint64_t *)ctx->dup_acc[1], ctx->dup_n, max_bin, out->copies_after, &out->distinct_after);
@@ -169,10 +144,9 @@ int rc_dup_census_end(rc_ctx *ctx)
         rc_set_error(ctx, "dup_census_end: no census is open");
         return RC_ERR_STATE;
     }
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = dups_drain(ctx);  // (a lane's key kernels may still write its slot's scratch)
-    std::lock_guard<std::mutex> lk(ctx->dup_mutex);
-    rc_dups_release(ctx);
+    const int rc = rc_drain(ctx);  // (a lane's key kernels may still write its slot's scratch)
+    std::lock_guard<std::mutex> lk(ctx->obs_mutex);
+    dups_release(ctx);
     return rc;
 }
 
@@ -216,14 +190,13 @@ int rc_dup_census_merge(rc_ctx *dst, rc_ctx *src)
         return RC_ERR_STATE;
     }
     RC_CHECK_HIP(dst, hipSetDevice(src->device));
-    if (dups_drain(src)) {
+    if (rc_drain(src)) {
         rc_set_error(dst, "dup_census_merge: the source context's work did not complete: %s", rc_last_error(src));
         return RC_ERR_HIP;
     }
-    RC_CHECK_HIP(dst, hipSetDevice(dst->device));
-    if (const int rc = dups_drain(dst)) return rc;
-    std::lock(dst->dup_mutex, src->dup_mutex);
-    std::lock_guard<std::mutex> l1(dst->dup_mutex, std::adopt_lock), l2(src->dup_mutex, std::adopt_lock);
+    if (const int rc = rc_drain(dst)) return rc;  // (and dst's device is current again)
+    std::lock(dst->obs_mutex, src->obs_mutex);
+    std::lock_guard<std::mutex> l1(dst->obs_mutex, std::adopt_lock), l2(src->obs_mutex, std::adopt_lock);
     const size_t n = src->dup_n;
     if (!n) return RC_OK;
     if (const int rc = dups_grow(dst, dst, n)) return rc;

@@ -68,10 +68,6 @@ struct rc_slot {
     // page-locked, and the fix count's landing place
     rc_slot_out out;
     rc_dbuf d_packed, d_exc, d_fix;
-    // correction report: a packed / resident batch's counts wait here until its wait accepts it (a batch that did not fit its
-    // fix list comes again, and only then counts); rep_staged: this batch left some
-    rc_dbuf d_rep;
-    bool rep_staged = false;
     rc_hbuf p_in, p_fix, p_nfix;
     // weak-k-mer profile of the batch in flight (rc_weak_profile_into): the caller's array (nullptr: none asked for), the 16
     // bytes per read in HBM, and their staging where the caller's array is not page-locked
@@ -79,13 +75,9 @@ struct rc_slot {
     bool weak_pinned = false;
     rc_dbuf d_weak;
     rc_hbuf p_weak;
-    // duplicate census: the keys of the batch in flight, dup_units before | dup_units after, until its wait accepts it
-    // (dup_units == 0: none were taken); dup_gen: the census they were taken for
-    rc_dbuf d_dup;
-    size_t dup_units = 0;
-    uint64_t dup_gen = 0;
-    // trust profile: the counts of the batch in flight, before | after, until its wait accepts it
-    rc_trust_staged trust;
+    // what the batch observers staged for the batch in flight, until its wait accepts it (a packed / resident batch that did
+    // not fit its fix list comes again, and only then counts)
+    rc_batch_observed obs;
     uint32_t fix_room = 0;
     bool fix_pinned = false;
 };
@@ -126,9 +118,25 @@ static inline int rc_concat_offsets(const rc_batch *b, size_t bytes1, uint32_t *
 
 extern "C" {  // (defined inside the units' extern "C" blocks)
 // rc_api_batch.hip
-// qual_split / qual_base2 (quality-bit mode only): arena bytes from qual_split on have their bits at byte qual_base2 of d_qual;
-// qual_bits: -1 = as rc_set_quality_bits says, 0 / 1 = this batch's quality arena holds bytes / bits (the packed boundary)
-int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits = -1);
+// check: what every correction entry point refuses of a batch descriptor with reads in it (status and error text).  impl: the
+// correction kernels over a batch that passed it, on ctx's stream with ctx's device current -- only rc_correct_observed calls
+// the two.  qual_split / qual_base2 (quality-bit mode only): arena bytes from qual_split on have their bits at byte qual_base2
+// of d_qual; qual_bits: -1 = as rc_set_quality_bits says, 0 / 1 = this batch's quality arena holds bytes / bits (the packed boundary)
+int rc_correct_check(rc_ctx *ctx, const rc_device_batch *b);
+int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits);
+// rc_api_observe.hip -- the one place the batch observers (correction report, duplicate census, trust profile, recount
+// follow) are hooked in.  ctx is the context the batch runs in (a context or one of its slot lanes).
+// rc_correct_observed: what every batch entry point does with its batch once the bases lie in b->d_seq -- rc_correct_check
+// (a refused batch reaches no observer; an empty one is RC_OK with nothing staged), then on ctx's stream the observers' look at
+// the arena as it is, rc_correct_device_impl, and their look at it as corrected, staged into o.  stage_report: the report's
+// counts wait in o too (a batch whose wait may refuse it), else they go straight into the report.
+// rc_batch_completed: the batch has completed and is accepted -- its corrected arena to the recount session (d_seq == nullptr:
+// not for this entry point), then what o holds into the census, the profile and the report, o empty afterwards; once per batch.
+int rc_correct_observed(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits, rc_batch_observed *o,
+                        bool stage_report);
+int rc_batch_completed(rc_ctx *ctx, rc_batch_observed *o, const void *d_seq, size_t nbytes);
+// o->drop(parts, free_bufs) for the rc_batch_observed of ctx, of its slots, and of its lanes and their slots
+void rc_observed_drop_all(rc_ctx *ctx, int parts, bool free_bufs);
 // rc_api_slots.hip
 int rc_hbuf_reserve(rc_ctx *ctx, rc_hbuf *h, size_t bytes);
 bool rc_is_pinned(const void *p, size_t bytes);
@@ -139,32 +147,26 @@ int rc_slots_init(rc_ctx *ctx);
 rc_ctx *rc_slot_lane(rc_ctx *ctx, int slot, bool create, bool refresh);
 // the lane's error text and summary counters seen through the parent
 void rc_lane_error(rc_ctx *ctx, const rc_ctx *lane);
+// The observers' own steps, called from rc_correct_observed / rc_batch_completed (and, the report's first two, from
+// rc_correct_read, whose one read is no batch of the run).  All do nothing while their observer is not armed; the accumulator
+// is that of rc_home(ctx), the context the batch was submitted to.
 // rc_api_table.hip
-// rc_recount_follow: a batch has completed in ctx (a context or one of its slot lanes) and its corrected arena lies in d_seq --
-// appended to the open session of the context the batch was submitted to, on ctx's own stream; nothing without a session
+// rc_recount_follow: the corrected arena in d_seq appended to the open session, on ctx's own stream; nothing without a session
 int rc_recount_take(rc_ctx *ctx, const void *d_seq, size_t nbytes);
-// rc_api_report.hip -- the correction report.  ctx is the context the batch runs in (a context or one of its slot lanes); the
-// report is that of the context the batch was submitted to.  All three do nothing while no report is armed.
-// snapshot: before the first correction kernel, on ctx's stream (rc_correct_device_impl does it for the batch entry points).
-// count: behind the last correction kernel -- the batch launched last on ctx against its snapshot, straight into the report
-// (staged == nullptr) or into `staged` (zeroed first), *did = something was launched.  commit: a staged batch into the report.
-int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes);
-int rc_report_count(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits, rc_dbuf *staged, bool *did);
+// rc_api_report.hip -- snapshot: the arena as it is, copied on ctx's stream; *snap = where (nullptr: none was taken).
+// count: the batch against that snapshot, straight into the report (stage == nullptr) or into stage->rep (zeroed first;
+// stage->rep_staged = something was launched).  commit: a staged block into the report.
+int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint8_t **snap);
+int rc_report_count(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits, const uint8_t *snap,
+                    rc_batch_observed *stage);
 int rc_report_commit(rc_ctx *ctx, const rc_dbuf *staged);
 void rc_report_release(rc_ctx *ctx);
-// rc_api_dups.hip -- the duplicate census.  ctx is the context the batch runs in (a context or one of its slot lanes); the
-// census is that of the context the batch was submitted to.  All do nothing while no census is open.
-// stage: the keys of the batch's arena as it is now, on ctx's stream, into keys (version 0: before the first correction
-// kernel -- reserves keys for both versions and sets *units / *gen; version 1: behind the last one).  commit: a completed
-// batch's staged keys appended to the census, complete on return; *units = 0 afterwards.
-int rc_dups_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_dbuf *keys, size_t *units, uint64_t *gen);
-int rc_dups_commit(rc_ctx *ctx, const rc_dbuf *keys, size_t *units, uint64_t gen);
-void rc_dups_release(rc_ctx *ctx);
-// rc_api_trust.hip -- the trust profile by read position, hooked in where the duplicate census is: stage (version 0 in front
-// of the first correction kernel: zeroes st's two rc_trust_counts and counts the arena as it is into the first; version 1
-// behind the last one: into the second), both on ctx's stream; commit: a completed batch's staged counts added to the profile
-// of the context the batch was submitted to, complete on return.  All do nothing while no profile is open.
+// rc_api_dups.hip -- stage: the keys of the batch's arena as it is now, on ctx's stream, into o->dup_keys (version 0 reserves
+// them for both versions and sets o->dup_units / dup_gen).  commit: appended to the census, complete on return; o->dup_units = 0.
+int rc_dups_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_batch_observed *o);
+int rc_dups_commit(rc_ctx *ctx, rc_batch_observed *o);
+// rc_api_trust.hip -- stage: version 0 zeroes st's two rc_trust_counts and counts the arena as it is into the first, version 1
+// into the second, on ctx's stream.  commit: the pair added to the profile, complete on return.
 int rc_trust_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_trust_staged *st);
 int rc_trust_commit(rc_ctx *ctx, rc_trust_staged *st);
-void rc_trust_release(rc_ctx *ctx);
 }

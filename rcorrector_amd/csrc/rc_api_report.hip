@@ -6,7 +6,8 @@
 // batch's own kernels -- so a slot's arena, qualities and offsets are done with before the event its wait waits for.  The
 // byte entry points have no second submission and count straight into the report.  A packed or resident batch may come
 // back with RC_STATUS_NOSPACE and be submitted again: its counts go to a staging block of the slot and reach the report when
-// the wait accepts the batch (rc_report_commit, where rc_recount_take sits) -- once, however often it was submitted.  Slot
+// the wait accepts the batch (rc_report_commit) -- once, however often it was submitted.  The three steps are called from
+// rc_correct_observed and rc_batch_completed (rc_api_observe.hip), which say where they sit for every entry point.  Slot
 // lanes are contexts on streams of their own: they add to the report of the context they serve with device-scope atomics.
 // The two paths differ in one respect: a byte batch is in the report once rc_submit has queued its kernels -- if a later step
 // of that submit fails, or the caller never waits, it has been counted all the same -- while a staged batch counts only when
@@ -16,33 +17,30 @@
 
 extern "C" {
 
-static rc_ctx *report_home(rc_ctx *ctx) { return ctx->is_lane && ctx->lane_parent ? ctx->lane_parent : ctx; }
-
-int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes)
+int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint8_t **snap_out)
 {
-    ctx->rep_snap_cur = nullptr;
-    if (!report_home(ctx)->rep_acc || !nbytes) return RC_OK;
+    *snap_out = nullptr;
+    if (!rc_home(ctx)->rep_acc || !nbytes) return RC_OK;
     // at the arena's alignment modulo 16: the kernel reads both in aligned 16-byte pieces (up to 15 bytes on either side)
     const size_t lead = (size_t)((uintptr_t)d_seq & 15u);
     if (const int rc = rc_dbuf_reserve(ctx, &ctx->rep_snap, nbytes + 64)) return rc;
     uint8_t *snap = (uint8_t *)ctx->rep_snap.p + lead;
     RC_CHECK_HIP(ctx, hipMemcpyAsync(snap, d_seq, nbytes, hipMemcpyDeviceToDevice, ctx->stream));
-    ctx->rep_snap_cur = snap;
+    *snap_out = snap;
     return RC_OK;
 }
 
-int rc_report_count(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits, rc_dbuf *staged, bool *did)
+int rc_report_count(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits, const uint8_t *snap,
+                    rc_batch_observed *stage)
 {
-    if (did) *did = false;
-    const uint8_t *snap = ctx->rep_snap_cur;
-    ctx->rep_snap_cur = nullptr;
-    rc_ctx *home = report_home(ctx);
+    if (stage) stage->rep_staged = false;
+    rc_ctx *home = rc_home(ctx);
     if (!snap || !home->rep_acc || !b->n_reads) return RC_OK;
     unsigned long long *out = home->rep_acc;
-    if (staged) {
-        if (const int rc = rc_dbuf_reserve(ctx, staged, RC_REPORT_WORDS * 8)) return rc;
-        RC_CHECK_HIP(ctx, hipMemsetAsync(staged->p, 0, RC_REPORT_WORDS * 8, ctx->stream));
-        out = (unsigned long long *)staged->p;
+    if (stage) {
+        if (const int rc = rc_dbuf_reserve(ctx, &stage->rep, RC_REPORT_WORDS * 8)) return rc;
+        RC_CHECK_HIP(ctx, hipMemsetAsync(stage->rep.p, 0, RC_REPORT_WORDS * 8, ctx->stream));
+        out = (unsigned long long *)stage->rep.p;
     }
     rc_device_batch_args a = rc_device_batch_args();
     a.mode = b->mode;
@@ -56,13 +54,13 @@ int rc_report_count(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, 
     a.off = b->d_off;
     a.ret = b->d_ret;
     if (const int rc = rc_launch_change_report(ctx, a, snap, out)) return rc;
-    if (did) *did = true;
+    if (stage) stage->rep_staged = true;
     return RC_OK;
 }
 
 int rc_report_commit(rc_ctx *ctx, const rc_dbuf *staged)
 {
-    rc_ctx *home = report_home(ctx);
+    rc_ctx *home = rc_home(ctx);
     if (!home->rep_acc || !staged->p) return RC_OK;
     return rc_launch_report_commit(ctx, (const unsigned long long *)staged->p, home->rep_acc);
 }
@@ -73,16 +71,6 @@ void rc_report_release(rc_ctx *ctx)
     ctx->rep_acc = nullptr;
     if (ctx->rep_snap.p) (void)hipFree(ctx->rep_snap.p);
     ctx->rep_snap = rc_dbuf();
-    ctx->rep_snap_cur = nullptr;
-}
-
-// the report kernels of ctx and its lanes have run
-static int report_drain(rc_ctx *ctx)
-{
-    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (rc_ctx *ln : ctx->lane)
-        if (ln) RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream));
-    return RC_OK;
 }
 
 int rc_change_report_begin(rc_ctx *ctx)
@@ -112,8 +100,7 @@ int rc_change_report_get(rc_ctx *ctx, rc_change_report *out)
         return RC_ERR_STATE;
     }
     static_assert(sizeof(rc_change_report) == RC_REPORT_WORDS * 8, "the accumulator is an rc_change_report");
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (const int rc = report_drain(ctx)) return rc;
+    if (const int rc = rc_drain(ctx)) return rc;  // (the report kernels of ctx and its lanes have run)
     RC_CHECK_HIP(ctx, hipMemcpy(out, ctx->rep_acc, sizeof *out, hipMemcpyDeviceToHost));
     return RC_OK;
 }
@@ -125,18 +112,12 @@ int rc_change_report_end(rc_ctx *ctx)
         rc_set_error(ctx, "change_report_end: the report is not armed");
         return RC_ERR_STATE;
     }
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = report_drain(ctx);  // (a lane may still be adding to the accumulator)
+    const int rc = rc_drain(ctx);  // (a lane may still be adding to the accumulator)
     rc_report_release(ctx);
     for (rc_ctx *ln : ctx->lane)
         if (ln) rc_report_release(ln);
     // a packed / resident batch still in flight was counted for this report: its staged counts go with it
-    auto drop_staged = [](rc_ctx *c) {
-        if (c && c->slots)
-            for (int s = 0; s < RC_MAX_SLOTS; ++s) c->slots[s].rep_staged = false;
-    };
-    drop_staged(ctx);
-    for (rc_ctx *ln : ctx->lane) drop_staged(ln);
+    rc_observed_drop_all(ctx, RC_OBS_REPORT, false);
     return rc;
 }
 

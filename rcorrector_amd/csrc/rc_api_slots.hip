@@ -39,8 +39,7 @@ static int slot_acquire(rc_ctx_full *ctx, int slot, const char *name, const char
         return RC_ERR_STATE;
     }
     sl.weak_out = nullptr;  // (slot_download sets it for a batch that has a weak-profile registration)
-    sl.dup_units = 0;       // (rc_dups_stage sets it for a batch that a duplicate census is open for)
-    sl.trust.staged = false;  // (rc_trust_stage: likewise, for a trust profile)
+    sl.obs.reset();         // (rc_correct_observed stages into it what the armed observers take of the batch)
     *out = &sl;
     return RC_OK;
 }
@@ -194,14 +193,8 @@ static int slot_wait_fix_list(rc_ctx_full *ctx, rc_slot &sl, const char *name)
         rc_set_error(ctx, "%s: %u substitutions, room for %u (fix_cap)", name, n_fix, cap);
         return RC_ERR_NOSPACE;
     }
-    // rc_recount_follow: before the slot can be reused (a batch that did not fit its fix list comes again and is taken then)
-    if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;
-    if (const int frc = rc_dups_commit(ctx, &sl.d_dup, &sl.dup_units, sl.dup_gen)) return frc;  // the duplicate census: likewise
-    if (const int frc = rc_trust_commit(ctx, &sl.trust)) return frc;  // the trust profile: likewise
-    if (sl.rep_staged) {  // the correction report: this submission is the one that counts
-        sl.rep_staged = false;
-        if (const int frc = rc_report_commit(ctx, &sl.d_rep)) return frc;
-    }
+    // the observers: before the slot can be reused, and only now (a batch that did not fit its fix list comes again and counts then)
+    if (const int frc = rc_batch_completed(ctx, &sl.obs, sl.d_seq.p, sl.arena_bytes)) return frc;
     slot_results_back(sl);
     if (!sl.fix_pinned && n_fix) {
         memcpy(sl.out.fix_pos, sl.p_fix.p, (size_t)n_fix * 4);
@@ -295,14 +288,8 @@ static int submit_bytes(rc_ctx_full *ctx, const rc_batch *b, int slot)
     RC_CHECK_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.e_h2d, 0));
     const rc_device_batch db = rc_device_batch_over(b->mode, total, nbytes, max_len, d_seq, d_qual, (const uint32_t *)sl.d_off.p, (int32_t *)sl.d_res.p);
     const uint32_t qsplit = qbits && b->mode == 1 ? (uint32_t)sl.bytes1 : 0xFFFFFFFFu;
-    // (the duplicate census: the keys of the bases as uploaded, and behind the last kernel those of the bases as corrected)
-    if ((rc = rc_dups_stage(ctx, &db, 0, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
-    if ((rc = rc_trust_stage(ctx, &db, 0, &sl.trust))) return rc;  // (the trust profile: the same two places)
-    if ((rc = rc_correct_device_impl(ctx, &db, qsplit, (uint32_t)qbase2))) return rc;
-    if ((rc = rc_dups_stage(ctx, &db, 1, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
-    if ((rc = rc_trust_stage(ctx, &db, 1, &sl.trust))) return rc;
     // (the correction report: no second submission on this path -- counted here, before the event rc_wait waits for)
-    if ((rc = rc_report_count(ctx, &db, qsplit, (uint32_t)qbase2, -1, nullptr, nullptr))) return rc;
+    if ((rc = rc_correct_observed(ctx, &db, qsplit, (uint32_t)qbase2, -1, &sl.obs, false))) return rc;
     // the corrected arena, then the results: always to the caller's four arrays one by one
     rc = slot_download(ctx, sl, false, [&]() -> int {
         char *o_seq1 = sl.seq_pinned ? b->seq : (char *)sl.p_seq.p;
@@ -331,9 +318,7 @@ static int wait_bytes(rc_ctx_full *ctx, int slot)
     if (sl.total_reads == 0) return RC_OK;
     RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     RC_CHECK_HIP(ctx, hipEventSynchronize(sl.e_done));
-    if (const int frc = rc_recount_take(ctx, sl.d_seq.p, sl.arena_bytes)) return frc;  // (rc_recount_follow: before the slot can be reused)
-    if (const int frc = rc_dups_commit(ctx, &sl.d_dup, &sl.dup_units, sl.dup_gen)) return frc;  // (the duplicate census: likewise)
-    if (const int frc = rc_trust_commit(ctx, &sl.trust)) return frc;  // (the trust profile: likewise)
+    if (const int frc = rc_batch_completed(ctx, &sl.obs, sl.d_seq.p, sl.arena_bytes)) return frc;  // (the observers: before the slot can be reused)
     if (!sl.seq_pinned) {
         memcpy(sl.b.seq, sl.p_seq.p, sl.bytes1);
         if (sl.b.mode == 1) memcpy(sl.b.seq2, (char *)sl.p_seq.p + sl.bytes1, sl.bytes2);
@@ -436,14 +421,8 @@ static int submit_packed(rc_ctx_full *ctx, rc_packed_batch *b, int slot)
     if (!h_qb) RC_CHECK_HIP(ctx, hipMemsetAsync(sl.d_qual.p, 0, nbytes, ctx->stream));  // FASTA: qual[0] == 0 (Reads.h:224-266)
     const rc_device_batch db = rc_device_batch_over(b->mode, total, nbytes, max_len, d_seq, (const uint8_t *)sl.d_qual.p, (const uint32_t *)sl.d_off.p,
                                                     (int32_t *)sl.d_res.p);
-    // (the duplicate census: the keys of the bases as they arrived, and behind the last kernel those of the bases as corrected)
-    if ((rc = rc_dups_stage(ctx, &db, 0, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
-    if ((rc = rc_trust_stage(ctx, &db, 0, &sl.trust))) return rc;  // (the trust profile: the same two places)
-    if ((rc = rc_correct_device_impl(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0))) return rc;
-    if ((rc = rc_dups_stage(ctx, &db, 1, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
-    if ((rc = rc_trust_stage(ctx, &db, 1, &sl.trust))) return rc;
     // (the correction report: staged, the wait decides whether this submission is the one that counts)
-    if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0, &sl.d_rep, &sl.rep_staged))) return rc;
+    if ((rc = rc_correct_observed(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0, &sl.obs, true))) return rc;
     uint32_t *d_fix_pos, *d_nfix = (uint32_t *)sl.d_fix.p;
     uint8_t *d_fix_chr;
     if ((rc = slot_fix_list_target(ctx, sl, &d_fix_pos, &d_fix_chr))) return rc;
@@ -536,14 +515,8 @@ static int submit_resident(rc_ctx_full *ctx, rc_resident_batch *b, int slot)
     if (!h_qb) RC_CHECK_HIP(ctx, hipMemsetAsync(sl.d_qual.p, 0, nbytes, ctx->stream));  // FASTA: qual[0] == 0 (Reads.h:224-266)
     const rc_device_batch db = rc_device_batch_over(b->mode, total, nbytes, max_len, d_seq, (const uint8_t *)sl.d_qual.p, (const uint32_t *)sl.d_off.p,
                                                     (int32_t *)sl.d_res.p);
-    // (the duplicate census: the keys of the bases as they arrived, and behind the last kernel those of the bases as corrected)
-    if ((rc = rc_dups_stage(ctx, &db, 0, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
-    if ((rc = rc_trust_stage(ctx, &db, 0, &sl.trust))) return rc;  // (the trust profile: the same two places)
-    if ((rc = rc_correct_device_impl(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0))) return rc;
-    if ((rc = rc_dups_stage(ctx, &db, 1, &sl.d_dup, &sl.dup_units, &sl.dup_gen))) return rc;
-    if ((rc = rc_trust_stage(ctx, &db, 1, &sl.trust))) return rc;
     // (the correction report: staged, the wait decides whether this submission is the one that counts)
-    if ((rc = rc_report_count(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0, &sl.d_rep, &sl.rep_staged))) return rc;
+    if ((rc = rc_correct_observed(ctx, &db, 0xFFFFFFFFu, 0, h_qb ? 1 : 0, &sl.obs, true))) return rc;
     uint32_t *d_fix_pos, *d_nfix = (uint32_t *)sl.d_fix.p;
     uint8_t *d_fix_chr;
     if ((rc = slot_fix_list_target(ctx, sl, &d_fix_pos, &d_fix_chr))) return rc;

@@ -442,13 +442,9 @@ int rc_table_count_arenas(const rc_ctx *ctx, size_t *n_arenas, uint64_t *bytes, 
 int rc_table_count_release(rc_ctx *ctx)
 {
     if (!ctx) return RC_ERR_ARG;
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a batch still reading them)
-    for (rc_ctx *ln : ctx->lane) {  // the slot lanes hold copies of the descriptors and run on streams of their own
-        if (!ln) continue;
-        RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream));
-        ln->kept.arenas.clear();
-    }
+    if (const int rc = rc_drain(ctx)) return rc;  // (a batch still reading them, here or in a slot lane)
+    for (rc_ctx *ln : ctx->lane)  // the slot lanes hold copies of the descriptors
+        if (ln) ln->kept.arenas.clear();
     ctx->kept.release();
     return RC_OK;
 }
@@ -747,7 +743,7 @@ int rc_recount_follow(rc_ctx *ctx, int on)
 
 int rc_recount_take(rc_ctx *ctx, const void *d_seq, size_t nbytes)
 {
-    rc_ctx *home = ctx->is_lane && ctx->lane_parent ? ctx->lane_parent : ctx;
+    rc_ctx *home = rc_home(ctx);
     if (!home->rec_active || !home->rec_follow || !nbytes) return RC_OK;
     const int rc = rc_recount_append(home, static_cast<const uint8_t *>(d_seq), nbytes, true, ctx->stream);
     if (rc && home != ctx) rc_lane_error(ctx, home);  // (the wait reports through the lane)
@@ -923,18 +919,18 @@ int rc_set_run_params(rc_ctx *ctx, double error_rate, char bad_quality)
     uint32_t *steps = steps_v.data();
     rc_bound_steps_build(error_rate, steps);
     for (int v = 0; v < RC_BS_INLINE; ++v) ctx->P.bs[v] = steps[v];
-    // ... and the whole table stays in device memory for the thresholds beyond those
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t steps_bytes = (size_t)RC_BOUND_STEPS * sizeof(uint32_t);
-    int rc = rc_dbuf_reserve(ctx, &ctx->bs_dev, steps_bytes + RC_BOUND_SMALL);
+    // ... and the whole table stays in device memory for the thresholds beyond those.  A batch in flight, here or in a slot
+    // lane, may still read the old one: drained before the buffer can be reallocated or overwritten
+    int rc = rc_drain(ctx);
     if (rc) return rc;
+    const size_t steps_bytes = (size_t)RC_BOUND_STEPS * sizeof(uint32_t);
+    if ((rc = rc_dbuf_reserve(ctx, &ctx->bs_dev, steps_bytes + RC_BOUND_SMALL))) return rc;
     // ... and behind it the bound itself for small counts (rc_run_params::bound_small), again the host's arithmetic
     uint8_t small[RC_BOUND_SMALL];
     for (int c = 0; c < RC_BOUND_SMALL; ++c) {
         const int v = rc_bound_i(c, error_rate);
         small[c] = v >= 0 && v < 255 ? (uint8_t)v : (uint8_t)255;
     }
-    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (a batch in flight may still read the old table)
     RC_CHECK_HIP(ctx, hipMemcpy(ctx->bs_dev.p, steps, steps_bytes, hipMemcpyHostToDevice));
     RC_CHECK_HIP(ctx, hipMemcpy((char *)ctx->bs_dev.p + steps_bytes, small, RC_BOUND_SMALL, hipMemcpyHostToDevice));
     ctx->P.bs_ext = getenv("RC_NO_BS_EXT") ? nullptr : (const uint32_t *)ctx->bs_dev.p;

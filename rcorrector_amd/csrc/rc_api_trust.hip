@@ -5,9 +5,10 @@
 // Where the counts go: a batch's BEFORE counts are taken on the stream of the context it runs in once its bases are in HBM
 // and before the first correction kernel, its AFTER counts behind the last one (rc_trust_stage), both into an rc_trust_counts
 // pair of the slot (or of the context, for the entry points that have no slot), zeroed first.  They are added to the profile
-// when the batch completes (rc_trust_commit, where rc_dups_commit sits) -- once, however often a batch that did not fit its
-// fix list was submitted.  Slot lanes are contexts on streams of their own: they add to the profile of the context they serve
-// under its dup_mutex, and a commit is complete on return, so two lanes never add at once and a slot's pair is free again.
+// when the batch completes (rc_trust_commit) -- once, however often a batch that did not fit its fix list was submitted.  Both
+// steps are called from one place each, rc_correct_observed and rc_batch_completed (rc_api_observe.hip), which say where they
+// sit for every entry point.  Slot lanes are contexts on streams of their own: they add to the profile of the context they serve
+// under its obs_mutex, and a commit is complete on return, so two lanes never add at once and a slot's pair is free again.
 #include "rc_api_internal.h"
 
 #include <cstddef>
@@ -25,19 +26,12 @@ static_assert(offsetof(rc_trust_profile, after) == offsetof(rc_trust_profile, be
 
 extern "C" {
 
-static rc_ctx *trust_home(rc_ctx *ctx) { return ctx->is_lane && ctx->lane_parent ? ctx->lane_parent : ctx; }
-
 int rc_trust_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_trust_staged *st)
 {
     if (version == 0) {
         st->staged = false;
-        rc_ctx *home = trust_home(ctx);
+        rc_ctx *home = rc_home(ctx);
         if (!home->trust_open) return RC_OK;
-        // (what rc_correct_device_impl refuses is refused there, uncounted)
-        if (!b->n_reads || b->mode < 0 || b->mode > 2 || (b->mode != 0 && (b->n_reads & 1u)) || !b->d_seq || !b->d_off || b->nbytes >= (1ull << 32) ||
-            !ctx->d_buckets)
-            return RC_OK;
-        RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
         if (const int rc = rc_dbuf_reserve(ctx, &st->buf, 2 * sizeof(rc_trust_counts))) return rc;
         RC_CHECK_HIP(ctx, hipMemsetAsync(st->buf.p, 0, 2 * sizeof(rc_trust_counts), ctx->stream));
         st->gen = home->trust_gen;
@@ -60,8 +54,8 @@ int rc_trust_commit(rc_ctx *ctx, rc_trust_staged *st)
 {
     if (!st->staged) return RC_OK;
     st->staged = false;
-    rc_ctx *home = trust_home(ctx);
-    std::lock_guard<std::mutex> lk(home->dup_mutex);
+    rc_ctx *home = rc_home(ctx);
+    std::lock_guard<std::mutex> lk(home->obs_mutex);
     if (!home->trust_open || home->trust_gen != st->gen) return RC_OK;  // (staged for a profile that has ended)
     if (const int rc = rc_launch_trust_add(ctx, st->buf.p, home->trust_acc, (uint32_t)(2 * RC_TRUST_WORDS))) return rc;
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -74,38 +68,21 @@ int rc_trust_commit(rc_ctx *ctx, rc_trust_staged *st)
     return RC_OK;
 }
 
-void rc_trust_release(rc_ctx *ctx)
+static void trust_release(rc_ctx *ctx)
 {
     if (ctx->trust_acc) (void)hipFree(ctx->trust_acc);
     ctx->trust_acc = nullptr;
     ctx->trust_open = false;
     auto scratch = [](rc_ctx *c) {
         if (!c) return;
-        rc_dbuf *bufs[] = {&c->trust_planes, &c->trust_part, &c->trust_tmp.buf};
-        for (rc_dbuf *b : bufs) {
+        for (rc_dbuf *b : {&c->trust_planes, &c->trust_part}) {
             if (b->p) (void)hipFree(b->p);
             *b = rc_dbuf();
         }
-        c->trust_tmp.staged = false;
-        if (c->slots)
-            for (int s = 0; s < RC_MAX_SLOTS; ++s) {
-                rc_slot &sl = c->slots[s];
-                if (sl.trust.buf.p) (void)hipFree(sl.trust.buf.p);
-                sl.trust.buf = rc_dbuf();
-                sl.trust.staged = false;
-            }
     };
     scratch(ctx);
     for (rc_ctx *ln : ctx->lane) scratch(ln);
-}
-
-// what ctx and its lanes have queued has run
-static int trust_drain(rc_ctx *ctx)
-{
-    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (rc_ctx *ln : ctx->lane)
-        if (ln) RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream));
-    return RC_OK;
+    rc_observed_drop_all(ctx, RC_OBS_TRUST, true);  // (the staged counts of ctx, its lanes and their slots)
 }
 
 int rc_trust_profile_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_off, uint32_t n_reads, uint64_t nbytes, int32_t max_read_len,
@@ -152,7 +129,7 @@ int rc_trust_profile_begin(rc_ctx *ctx, int32_t min_count)
         rc_set_error(ctx, "trust_profile_begin: min_count must be at least 1 (got %d)", min_count);
         return RC_ERR_ARG;
     }
-    std::lock_guard<std::mutex> lk(ctx->dup_mutex);
+    std::lock_guard<std::mutex> lk(ctx->obs_mutex);
     if (ctx->trust_open) {
         rc_set_error(ctx, "trust_profile_begin: a profile is open already (rc_trust_profile_end it first)");
         return RC_ERR_STATE;
@@ -187,9 +164,8 @@ int rc_trust_profile_get(rc_ctx *ctx, rc_trust_profile *out)
         rc_set_error(ctx, "trust_profile_get: out must not be NULL");
         return RC_ERR_ARG;
     }
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (const int rc = trust_drain(ctx)) return rc;
-    std::lock_guard<std::mutex> lk(ctx->dup_mutex);
+    if (const int rc = rc_drain(ctx)) return rc;
+    std::lock_guard<std::mutex> lk(ctx->obs_mutex);
     out->k = ctx->k;
     out->min_count = ctx->trust_min;
     out->reads[0] = ctx->trust_reads[0];
@@ -205,10 +181,9 @@ int rc_trust_profile_end(rc_ctx *ctx)
         rc_set_error(ctx, "trust_profile_end: no profile is open");
         return RC_ERR_STATE;
     }
-    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = trust_drain(ctx);  // (a lane's kernels may still write its slot's counts and its scratch)
-    std::lock_guard<std::mutex> lk(ctx->dup_mutex);
-    rc_trust_release(ctx);
+    const int rc = rc_drain(ctx);  // (a lane's kernels may still write its slot's counts and its scratch)
+    std::lock_guard<std::mutex> lk(ctx->obs_mutex);
+    trust_release(ctx);
     return rc;
 }
 

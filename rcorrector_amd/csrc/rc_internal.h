@@ -80,6 +80,23 @@ struct rc_trust_staged {
     int32_t min_count = 1;
 };
 
+// What the batch observers (rc_api_observe.hip) keep for one batch in flight, from the submit that staged it to the completion
+// that accepts it: the duplicate census's keys (dup_units before | dup_units after; 0: none were taken) and the census they
+// were taken for, the trust profile's counts, and the correction report's counts where they are staged (rep_staged: this batch
+// left some).  One per slot, and one per context for the entry points that have no slot.
+enum { RC_OBS_DUPS = 1, RC_OBS_TRUST = 2, RC_OBS_REPORT = 4, RC_OBS_ALL = 7 };
+struct rc_batch_observed {
+    rc_dbuf dup_keys;
+    size_t dup_units = 0;
+    uint64_t dup_gen = 0;
+    rc_trust_staged trust;
+    rc_dbuf rep;
+    bool rep_staged = false;
+    // nothing staged any more for these observers; free_bufs: their buffers go too
+    void drop(int parts, bool free_bufs);
+    void reset() { drop(RC_OBS_ALL, false); }
+};
+
 struct rc_kernel_timer {
     double ms = 0;       // accumulated
     uint64_t launches = 0;
@@ -152,19 +169,18 @@ struct rc_ctx {
     std::vector<uint64_t> spec_counted;
     // recount session (rc_recount_begin): a second counting session that builds no table -- its arenas in chunks of its own
     // (the counter's and the kept arenas are never touched), the bound its spectrum is binned to, and whether the batches
-    // that complete on this context (its slot lanes included: lane_parent) append their corrected arena (rc_recount_follow)
+    // that complete on this context (its slot lanes included: rc_home) append their corrected arena (rc_recount_follow)
     rc_arena_set rec;
     bool rec_active = false, rec_follow = false;
     uint32_t rec_bin = 0;
     std::mutex rec_mutex;
     rc_ctx *lane_parent = nullptr;  // a slot lane: the context whose slots it serves
     // correction report (rc_change_report_begin): the accumulator, RC_REPORT_WORDS 64-bit counts laid out as rc_change_report
-    // (nullptr: not armed; the batches of this context's slot lanes add to it too: lane_parent).  In the context a batch RUNS
-    // in (a lane included): the copy of its arena taken before the first correction kernel (grow-only), and where that copy
-    // of the batch launched last lies (nullptr: none was taken) -- all on that context's one compute stream
+    // (nullptr: not armed; the batches of this context's slot lanes add to it too: rc_home).  In the context a batch RUNS
+    // in (a lane included): the copy of its arena taken before the first correction kernel (grow-only), on that context's one
+    // compute stream
     unsigned long long *rep_acc = nullptr;
     rc_dbuf rep_snap;
-    const uint8_t *rep_snap_cur = nullptr;
     // weak-k-mer profile (rc_weak_profile_device / rc_weak_profile_into; kernels in rc_weak.hip).  weak_planes: the two bit planes
     // of the arena profiled last, scratch of the context the kernels run in (they serialise on its compute stream).  weak_reg:
     // per slot of THIS context's entry points, where the next batch submitted there leaves its reads' profile (out == nullptr:
@@ -177,30 +193,28 @@ struct rc_ctx {
     rc_dbuf weak_planes;
     rc_weak_reg weak_reg[4], weak_cur;
     // duplicate census (rc_dup_census_begin; kernels in rc_dups.hip).  In the context it was opened on (the batches of its slot
-    // lanes add to it too: lane_parent): the keys of every unit seen, version 0 = before and 1 = after correction, 16 bytes per
+    // lanes add to it too: rc_home): the keys of every unit seen, version 0 = before and 1 = after correction, 16 bytes per
     // unit each, dup_n units of dup_cap; dup_gen counts the begins (keys a batch staged for one census never reach the next).
-    // dup_mutex: the lanes' waits append concurrently.  In the context a batch RUNS in: dup_tmp, the keys (before | after) of
-    // the batch of an entry point that has no slot (rc_correct_device, rc_correct_batch_traced), dup_tmp_units of them
+    // obs_mutex: the lanes' waits append to the census and add to the trust profile concurrently.
     std::atomic<bool> dup_open{false};  // (read by the lanes' submits without the mutex)
     void *dup_acc[2] = {nullptr, nullptr};
     size_t dup_n = 0, dup_cap = 0;
     uint64_t dup_gen = 0;
-    std::mutex dup_mutex;
-    rc_dbuf dup_tmp;
-    size_t dup_tmp_units = 0;
-    uint64_t dup_tmp_gen = 0;
+    std::mutex obs_mutex;
     // trust profile (rc_trust_profile_begin; kernels in rc_trust.hip).  In the context it was opened on (the batches of its slot
-    // lanes add to it too: lane_parent): trust_acc, two rc_trust_counts in HBM (before | after), the reads seen per mate, the
-    // threshold, and trust_gen, which counts the begins; the lanes' waits add under dup_mutex.  In the context a batch or
+    // lanes add to it too: rc_home): trust_acc, two rc_trust_counts in HBM (before | after), the reads seen per mate, the
+    // threshold, and trust_gen, which counts the begins; the lanes' waits add under obs_mutex.  In the context a batch or
     // rc_trust_profile_device RUNS in: the bit planes and the wavefronts' partial counts of the arena profiled last (scratch,
-    // serialised on its compute stream), and trust_tmp, the staged counts of the batch of an entry point that has no slot
+    // serialised on its compute stream)
     std::atomic<bool> trust_open{false};  // (read by the lanes' submits without the mutex)
     void *trust_acc = nullptr;
     uint64_t trust_reads[2] = {0, 0};
     int32_t trust_min = 1;
     uint64_t trust_gen = 0;
     rc_dbuf trust_planes, trust_part;
-    rc_trust_staged trust_tmp;
+    // in the context a batch RUNS in: what the observers staged for the batch of an entry point that has no slot
+    // (rc_correct_device, rc_correct_batch_traced)
+    rc_batch_observed obs;
 
     // batch scratch
     rc_dbuf counts;   // int32 per arena byte
@@ -251,6 +265,10 @@ int rc_dbuf_reserve(rc_ctx *ctx, rc_dbuf *b, size_t bytes);
 rc_table_view rc_view(const rc_ctx *ctx);
 // frees the table this context owns (the allocation starts RC_TABLE_PREFIX_BYTES before d_buckets)
 void rc_table_release(rc_ctx *ctx);
+// the context a slot lane serves, else the context itself: where the accumulators of the batch observers and the recount session live
+static inline rc_ctx *rc_home(rc_ctx *ctx) { return ctx->is_lane && ctx->lane_parent ? ctx->lane_parent : ctx; }
+// ctx's device current, and what ctx and its slot lanes (streams of their own) have queued has run
+int rc_drain(rc_ctx *ctx);
 void rc_timer_begin(rc_ctx *ctx);
 void rc_timer_end(rc_ctx *ctx, int which);
 
