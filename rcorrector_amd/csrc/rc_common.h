@@ -184,6 +184,37 @@ RC_HD void rc_pack16m(const uint32_t (&w)[4], uint32_t &code, uint32_t &am, uint
     am = rc_compress_even16(~(r | (r >> 1)));
 }
 
+// ---- the k-byte window at position a of a staged tile (rc_device.h: rc_tile_stage, the arena-order probe kernels) ------------
+// The planes: code[c] = the 2-bit codes of bytes [16 c, 16 c + 16), first byte in the top bits; m_inv / m_nul = one bit per
+// byte (not one of ACGT -- a NUL included -- / a NUL), byte p at bit 31 - p % 32 of word p / 32.  The window is cut out of two
+// mask words and three code words, so the planes reach 32 bytes (the halo) and two more code words behind the last position
+// asked for.  nul: the window crosses a NUL -- a read's end: it is no k-mer of any read; bad: it holds a letter outside ACGT
+// (every window with `nul` is also `bad`); code: its 2k-bit code where it is neither, else 0.  NUL = false: a kernel without
+// a NUL plane (m_nul is not read, nul is false).  4 <= k <= 32.  tests/hostmath/tile_window.cpp: every k, every position.
+struct rc_tile_win {
+    bool nul, bad;
+    uint64_t code;
+};
+template <bool NUL = true>
+RC_HD rc_tile_win rc_tile_window(const uint32_t *code, const uint32_t *m_inv, const uint32_t *m_nul, int a, int k)
+{
+    const int mw = a >> 5, ms = a & 31;
+    rc_tile_win w = {false, false, 0};
+    if (NUL) w.nul = (((((uint64_t)m_nul[mw] << 32) | m_nul[mw + 1]) << ms) >> (64 - k)) != 0;
+    if (w.nul) {
+        w.bad = true;
+        return w;
+    }
+    w.bad = (((((uint64_t)m_inv[mw] << 32) | m_inv[mw + 1]) << ms) >> (64 - k)) != 0;
+    if (!w.bad) {
+        const int cw = a >> 4, cs = 2 * (a & 15);
+        uint64_t x = ((uint64_t)code[cw] << 32) | code[cw + 1];
+        if (cs) x = (x << cs) | ((uint64_t)code[cw + 2] >> (32 - cs));
+        w.code = x >> (64 - 2 * k);
+    }
+    return w;
+}
+
 // a letter as rc_read_state::base holds it: 0 1 2 3 = A C G T, 4 = N, 5 = anything else
 RC_HD int rc_base_code(uint32_t c)
 {

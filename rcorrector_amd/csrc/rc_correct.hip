@@ -260,25 +260,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     constexpr int RC_FUSED_STOP_ = -1;
 #endif
     RC_FUSED_CUT(0, s_lpos[t & 15] ^ s_gpos[t & 15] ^ s_rid[t & 15]);
-    for (uint32_t j = (uint32_t)t >> 6; j < nr; j += NT / 64) {  // copy, aligned dwords, outside bytes masked to NUL
-        if (!s_len1[j]) continue;
-        const uint32_t g0 = s_gpos[j], lp = s_lpos[j], g1 = g0 + s_len1[j] - 1;
-        const uint32_t w0 = g0 >> 2, w1 = (g1 + 3) >> 2;
-        for (uint32_t w = w0 + ((uint32_t)t & 63u); w < w1; w += 64u) {
-            uint32_t v;
-            if ((size_t)4 * w + 4 <= nbytes) {
-                v = *reinterpret_cast<const uint32_t *>(seq + (size_t)4 * w);
-            } else {
-                v = 0;
-                for (size_t q = 0; (size_t)4 * w + q < nbytes; ++q) v |= (uint32_t)seq[(size_t)4 * w + q] << (8 * q);
-            }
-            const uint32_t lo = 4 * w < g0 ? g0 - 4 * w : 0, hi = 4 * w + 4 > g1 ? 4 * w + 4 - g1 : 0;
-            uint32_t m = 0xFFFFFFFFu;
-            if (lo) m &= 0xFFFFFFFFu << (8 * lo);
-            if (hi) m &= 0xFFFFFFFFu >> (8 * hi);
-            s_raw[(lp >> 2) + (w - w0)] = v & m;
-        }
-    }
+    rc_tile_copy_reads<NT>(s_raw, s_gpos, s_lpos, s_len1, nr, seq, nbytes);
     __syncthreads();
     RC_FUSED_CUT(1, s_raw[t]);
     const uint32_t total = s_lpos[nr];

@@ -29,7 +29,8 @@ __device__ __forceinline__ uint32_t rc_count_slice(uint64_t key, uint32_t P)
     return (uint32_t)(((uint64_t)rc_hash(key ^ 0x9E3779B97F4A7C15ull) * P) >> 32);
 }
 
-// MODE 0: hist[slice] += valid k-mers of the tile; MODE 1: the canonical codes of slice `p` are appended to out
+// MODE 0: hist[slice] += valid k-mers of the tile; MODE 1: the canonical codes of slice `p` are appended to out.  k_probe's
+// tile (rc_device.h: rc_tile_stage) without the NUL plane; seq is 16-byte aligned.
 template <int MODE>
 __global__ __launch_bounds__(RC_PROBE_THREADS) void k_count_scan(const uint8_t *__restrict__ seq, size_t nbytes, int k, uint32_t P, uint32_t p,
                                                                  unsigned long long *__restrict__ hist, uint64_t *__restrict__ out,
@@ -41,35 +42,16 @@ __global__ __launch_bounds__(RC_PROBE_THREADS) void k_count_scan(const uint8_t *
     const size_t tile0 = (size_t)blockIdx.x * RC_PROBE_TILE;
     const int t = threadIdx.x;
     if (MODE == 0 && t < 64) s_hist[t] = 0;
-    for (int chunk = t; chunk < RC_PROBE_TILE / 16 + 2; chunk += RC_PROBE_THREADS) {
-        const size_t g = tile0 + (size_t)chunk * 16;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (g + 16 <= nbytes) {
-            v = *reinterpret_cast<const uint4 *>(seq + g);
-        } else if (g < nbytes) {
-            uint32_t w[4] = {0, 0, 0, 0};
-            for (size_t j = 0; g + j < nbytes; ++j) w[j >> 2] |= (uint32_t)seq[g + j] << (8 * (j & 3));
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        uint32_t code, inv, nul;
-        rc_pack16(v, code, inv, nul);
-        s_code[chunk] = code;
-        s_inv[chunk ^ 1] = (uint16_t)inv;  // NUL is also "not ACGT"
-    }
-    if (t < 2) s_code[RC_PROBE_TILE / 16 + 2 + t] = 0xFFFFFFFFu;
+    rc_tile_stage<false>(seq, 0, nbytes, tile0, s_code, s_inv, nullptr);  // no NUL plane: a NUL is also "not ACGT"
     __syncthreads();
     const uint32_t *m_inv = reinterpret_cast<const uint32_t *>(s_inv);
     // the canonical code of the window at tile position a, if it is a k-mer of a read, and its slice
     auto window = [&](int a, uint64_t &key, uint32_t &sl) -> bool {
         const size_t g = tile0 + (size_t)a;
         if (g + (size_t)k > nbytes) return false;
-        const int mw = a >> 5, ms = a & 31;
-        const uint64_t invw = (((uint64_t)m_inv[mw] << 32) | m_inv[mw + 1]) << ms;
-        if (invw >> (64 - k)) return false;
-        const int cw = a >> 4, cs = 2 * (a & 15);
-        uint64_t x = ((uint64_t)s_code[cw] << 32) | s_code[cw + 1];
-        if (cs) x = (x << cs) | ((uint64_t)s_code[cw + 2] >> (32 - cs));
-        key = rc_canonical(x >> (64 - 2 * k), k);
+        const rc_tile_win w = rc_tile_window<false>(s_code, m_inv, nullptr, a, k);
+        if (w.bad) return false;
+        key = rc_canonical(w.code, k);
         sl = rc_count_slice(key, P);
         return true;
     };

@@ -275,6 +275,87 @@ __device__ __forceinline__ void rc_pack16(const uint4 v, uint32_t &code, uint32_
 
 #define RC_PLIST_MAX_READS 64  // reads per workgroup of the list-driven probe kernels
 
+// ---- the tile of the probe kernels that walk arena positions (k_probe, k_probe_list, k_count_scan, k_weak_planes) -----------
+// TILE bytes plus a 32-byte halo in LDS as three planes -- s_code[TILE / 16 + 4], s_inv / s_nul[TILE / 16 + 4]: the 2-bit codes
+// and the not-ACGT / NUL bit masks that rc_tile_window (rc_common.h) cuts a position's k-mer out of.  NUL = false: a kernel
+// that keeps no NUL plane (a NUL is also "not ACGT"); s_nul is not touched.
+// rc_tile_pack: 16 staged bytes -> chunk `chunk` of the planes
+template <bool NUL = true>
+__device__ __forceinline__ void rc_tile_pack(const uint4 v, int chunk, uint32_t *s_code, uint16_t *s_inv, uint16_t *s_nul)
+{
+    uint32_t code, inv, nul;
+    rc_pack16(v, code, inv, nul);
+    s_code[chunk] = code;
+    s_inv[chunk ^ 1] = (uint16_t)inv;  // big-endian bit order inside each 32-bit mask word
+    if (NUL) s_nul[chunk ^ 1] = (uint16_t)nul;
+}
+
+// the two code words behind the halo: a window's third code word, whatever its position (never part of a k-mer)
+template <int TILE = RC_PROBE_TILE>
+__device__ __forceinline__ void rc_tile_sentinels(uint32_t *s_code)
+{
+    if (threadIdx.x < 2) s_code[TILE / 16 + 2 + threadIdx.x] = 0xFFFFFFFFu;
+}
+
+// rc_tile_stage: tile bytes [tile0, tile0 + TILE + 32) of an arena in global memory into the planes, by NT threads.  seq16 is
+// 16-byte aligned and the arena is bytes [lead, lead + nbytes) from there (lead < 16; 0 for an aligned arena); tile0 counts
+// from seq16.  Every 16-byte piece that holds a byte of the arena is loaded whole and aligned -- up to 15 bytes in front of
+// the arena and behind it are read, inside the memory page its first / last byte lies in -- and the bytes outside the arena
+// are masked to NULs: the planes a byte-by-byte read of the arena's ends would give, since a byte outside it is a NUL either
+// way.  A piece that holds no byte of the arena is not loaded (all NULs): no window reaches across the arena's ends.
+template <bool NUL = true, int TILE = RC_PROBE_TILE, int NT = RC_PROBE_THREADS>
+__device__ __forceinline__ void rc_tile_stage(const uint8_t *__restrict__ seq16, uint32_t lead, size_t nbytes, size_t tile0, uint32_t *s_code,
+                                              uint16_t *s_inv, uint16_t *s_nul)
+{
+    const size_t end = (size_t)lead + nbytes;
+    for (int chunk = threadIdx.x; chunk < TILE / 16 + 2; chunk += NT) {  // thread t: bytes [16t, 16t+16); threads 0..1 also the halo
+        const size_t g = tile0 + (size_t)chunk * 16;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (g < end) {
+            v = *reinterpret_cast<const uint4 *>(seq16 + g);
+            if (g < lead || g + 16 > end) {
+                uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 16; ++j)
+                    if (g + j < lead || g + j >= end) w[j >> 2] &= ~(0xFFu << (8 * (j & 3)));
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+        }
+        rc_tile_pack<NUL>(v, chunk, s_code, s_inv, s_nul);
+    }
+    rc_tile_sentinels<TILE>(s_code);
+}
+
+// rc_tile_copy_reads: the reads of a list-driven workgroup (NT threads) into its local arena s_raw (zeroed by the caller), read
+// j -- s_len1[j] bytes with its NUL, 0 = left out -- from arena byte s_gpos[j] to local byte s_lpos[j], which has the same
+// alignment modulo 4.  One 64-lane group per read, aligned dwords, bytes outside the read masked to NUL; the arena's last
+// dword is read byte by byte where nbytes is no multiple of 4.
+template <int NT>
+__device__ __forceinline__ void rc_tile_copy_reads(uint32_t *s_raw, const uint32_t *s_gpos, const uint32_t *s_lpos, const uint32_t *s_len1, uint32_t nr,
+                                                   const uint8_t *__restrict__ seq, size_t nbytes)
+{
+    const uint32_t t = threadIdx.x;
+    for (uint32_t j = t >> 6; j < nr; j += NT / 64) {
+        if (!s_len1[j]) continue;
+        const uint32_t g0 = s_gpos[j], lp = s_lpos[j], g1 = g0 + s_len1[j] - 1;  // [g0, g1): the bases
+        const uint32_t w0 = g0 >> 2, w1 = (g1 + 3) >> 2;
+        for (uint32_t w = w0 + (t & 63u); w < w1; w += 64u) {
+            uint32_t v;
+            if ((size_t)4 * w + 4 <= nbytes) {
+                v = *reinterpret_cast<const uint32_t *>(seq + (size_t)4 * w);
+            } else {
+                v = 0;
+                for (size_t q = 0; (size_t)4 * w + q < nbytes; ++q) v |= (uint32_t)seq[(size_t)4 * w + q] << (8 * q);
+            }
+            const uint32_t lo = 4 * w < g0 ? g0 - 4 * w : 0, hi = 4 * w + 4 > g1 ? 4 * w + 4 - g1 : 0;  // bytes to drop at either end
+            uint32_t m = 0xFFFFFFFFu;
+            if (lo) m &= 0xFFFFFFFFu << (8 * lo);
+            if (hi) m &= 0xFFFFFFFFu >> (8 * hi);
+            s_raw[(lp >> 2) + (w - w0)] = v & m;
+        }
+    }
+}
+
 // the live entry stored in slot s of bucket b, if any: its canonical code and count.  A key that was
 // Put more than once occupies several slots; the one a probe reaches first (the latest Put,
 // Store.h:55) is the table's entry, the others are dead.

@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -271,6 +272,16 @@ static inline rc_ctx *rc_home(rc_ctx *ctx) { return ctx->is_lane && ctx->lane_pa
 int rc_drain(rc_ctx *ctx);
 void rc_timer_begin(rc_ctx *ctx);
 void rc_timer_end(rc_ctx *ctx, int which);
+// f(std::bool_constant<ext>{}): the launch of a kernel that is compiled for tables with and without remainder-extension bits
+// (rc_device.h: EXT), written once -- rc_with_ext(ctx->ext, [&](auto ext) { ... k_probe<decltype(ext)::value> ... });
+template <class F>
+static inline void rc_with_ext(int ext, F &&f)
+{
+    if (ext)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
 
 // rc_table.hip
 int rc_build_table_from_device_pairs(rc_ctx *ctx, const uint64_t *d_canon, const int32_t *d_counts,

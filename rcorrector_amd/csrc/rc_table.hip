@@ -1153,8 +1153,9 @@ int rc_launch_tier_lists(rc_ctx *ctx, const rc_device_batch_args &a, int s_hi, i
 // read (reads are NUL-terminated inside the arena, so "inside one read" == "no NUL in the
 // window").  Windows holding a non-ACGT letter give 0 without touching the table (Store.h:61-62).
 // One 256-thread workgroup owns a 4 KiB tile of the arena: it stages the tile (+32 B halo) into
-// LDS as 2-bit codes plus two bit masks (non-ACGT, NUL), then every lane extracts its windows
-// with funnel shifts, canonicalises with bit-reverse and probes one 64-byte bucket.
+// LDS as 2-bit codes plus two bit masks (non-ACGT, NUL; rc_device.h: rc_tile_stage), then every lane cuts
+// its windows out of them (rc_common.h: rc_tile_window), canonicalises with bit-reverse and probes one bucket.
+// seq is 16-byte aligned.
 template <bool EXT>
 __global__ __launch_bounds__(RC_PROBE_THREADS) void k_probe(rc_table_view T, const uint8_t *__restrict__ seq,
                                                             size_t nbytes, int k, int32_t *__restrict__ counts)
@@ -1165,26 +1166,7 @@ __global__ __launch_bounds__(RC_PROBE_THREADS) void k_probe(rc_table_view T, con
     const size_t tile0 = (size_t)blockIdx.x * RC_PROBE_TILE;
     const int t = threadIdx.x;
 
-    // stage: thread t packs bytes [16t, 16t+16) of the tile; threads 0..1 also pack the halo
-    for (int chunk = t; chunk < RC_PROBE_TILE / 16 + 2; chunk += RC_PROBE_THREADS) {
-        const size_t g = tile0 + (size_t)chunk * 16;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (g + 16 <= nbytes) {
-            v = *reinterpret_cast<const uint4 *>(seq + g);
-        } else if (g < nbytes) {
-            uint32_t w[4] = {0, 0, 0, 0};
-            for (size_t j = 0; g + j < nbytes; ++j) w[j >> 2] |= (uint32_t)seq[g + j] << (8 * (j & 3));
-            v = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        uint32_t code, inv, nul;
-        rc_pack16(v, code, inv, nul);
-        s_code[chunk] = code;
-        s_inv[chunk ^ 1] = (uint16_t)inv;  // big-endian bit order inside each 32-bit mask word
-        s_nul[chunk ^ 1] = (uint16_t)nul;
-    }
-    if (t < 2) {
-        s_code[RC_PROBE_TILE / 16 + 2 + t] = 0xFFFFFFFFu;
-    }
+    rc_tile_stage(seq, 0, nbytes, tile0, s_code, s_inv, s_nul);
     __syncthreads();
     const uint32_t *m_inv = reinterpret_cast<const uint32_t *>(s_inv);
     const uint32_t *m_nul = reinterpret_cast<const uint32_t *>(s_nul);
@@ -1193,25 +1175,17 @@ __global__ __launch_bounds__(RC_PROBE_THREADS) void k_probe(rc_table_view T, con
     for (int a = t; a < RC_PROBE_TILE; a += RC_PROBE_THREADS) {
         const size_t g = tile0 + (size_t)a;
         if (g + (size_t)k > nbytes) break;
-        const int mw = a >> 5, ms = a & 31;
-        const uint64_t nulw = (((uint64_t)m_nul[mw] << 32) | m_nul[mw + 1]) << ms;
-        if (nulw >> (64 - k)) continue;  // window crosses a read boundary: not a k-mer of any read
-        const uint64_t invw = (((uint64_t)m_inv[mw] << 32) | m_inv[mw + 1]) << ms;
-        int cnt = 0;
-        if (!(invw >> (64 - k))) {
-            const int cw = a >> 4, cs = 2 * (a & 15);
-            uint64_t x = ((uint64_t)s_code[cw] << 32) | s_code[cw + 1];
-            if (cs) x = (x << cs) | ((uint64_t)s_code[cw + 2] >> (32 - cs));
-            const uint64_t code = x >> (64 - 2 * k);
-            cnt = rc_table_lookup<EXT>(T, rc_canonical(code, k));
-        }
+        const rc_tile_win w = rc_tile_window(s_code, m_inv, m_nul, a, k);
+        if (w.nul) continue;  // window crosses a read boundary: not a k-mer of any read
+        const int cnt = w.bad ? 0 : rc_table_lookup<EXT>(T, rc_canonical(w.code, k));
         __builtin_nontemporal_store(cnt, &counts[g]);  // streamed once: keep it out of the caches the table lives in
     }
 }
 
 // K1 over a list of reads (locality order): the workgroup's reads are copied into a local arena in
-// LDS -- each at the byte alignment it has in memory, NULs in between -- packed and probed as in
-// k_probe; a count goes to the position of its k-mer in the caller's arena.
+// LDS (rc_device.h: rc_tile_copy_reads) -- each at the byte alignment it has in memory, NULs in between -- and that arena is
+// k_probe's tile: the same planes (rc_tile_pack), the same window cut; a count goes to the position of its k-mer in the
+// caller's arena.
 // skip_hi >= 0: the reads of units (a read, or a pair: mode as in rc_kernel_args) whose longer read has at most skip_hi
 // bases are left out -- the fused probe + threshold kernel of the short tier has their counts (rc_correct.hip).
 template <bool EXT>
@@ -1260,53 +1234,20 @@ __global__ __launch_bounds__(RC_PROBE_THREADS) void k_probe_list(rc_table_view T
         s_lpos[nr] = lp;
     }
     __syncthreads();
-    // copy: one 64-lane group per read, aligned dwords, bytes outside the read masked to NUL
-    for (uint32_t j = (uint32_t)t >> 6; j < nr; j += RC_PROBE_THREADS / 64) {
-        if (!s_len1[j]) continue;
-        const uint32_t g0 = s_gpos[j], lp = s_lpos[j], g1 = g0 + s_len1[j] - 1;  // [g0, g1): the bases
-        const uint32_t w0 = g0 >> 2, w1 = (g1 + 3) >> 2;
-        for (uint32_t w = w0 + ((uint32_t)t & 63u); w < w1; w += 64u) {
-            uint32_t v;
-            if ((size_t)4 * w + 4 <= nbytes) {
-                v = *reinterpret_cast<const uint32_t *>(seq + (size_t)4 * w);
-            } else {
-                v = 0;
-                for (size_t q = 0; (size_t)4 * w + q < nbytes; ++q) v |= (uint32_t)seq[(size_t)4 * w + q] << (8 * q);
-            }
-            const uint32_t lo = 4 * w < g0 ? g0 - 4 * w : 0, hi = 4 * w + 4 > g1 ? 4 * w + 4 - g1 : 0;  // bytes to drop at either end
-            uint32_t m = 0xFFFFFFFFu;
-            if (lo) m &= 0xFFFFFFFFu << (8 * lo);
-            if (hi) m &= 0xFFFFFFFFu >> (8 * hi);
-            s_raw[(lp >> 2) + (w - w0)] = v & m;
-        }
-    }
+    rc_tile_copy_reads<RC_PROBE_THREADS>(s_raw, s_gpos, s_lpos, s_len1, nr, seq, nbytes);
     __syncthreads();
     const uint32_t total = s_lpos[nr];
-    for (int chunk = t; chunk < RC_PROBE_TILE / 16 + 2; chunk += RC_PROBE_THREADS) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(s_raw + 4 * chunk);
-        uint32_t code, inv, nul;
-        rc_pack16(v, code, inv, nul);
-        s_code[chunk] = code;
-        s_inv[chunk ^ 1] = (uint16_t)inv;
-        s_nul[chunk ^ 1] = (uint16_t)nul;
-    }
-    if (t < 2) s_code[RC_PROBE_TILE / 16 + 2 + t] = 0xFFFFFFFFu;
+    for (int chunk = t; chunk < RC_PROBE_TILE / 16 + 2; chunk += RC_PROBE_THREADS)
+        rc_tile_pack(*reinterpret_cast<const uint4 *>(s_raw + 4 * chunk), chunk, s_code, s_inv, s_nul);
+    rc_tile_sentinels(s_code);
     __syncthreads();
     const uint32_t *m_inv = reinterpret_cast<const uint32_t *>(s_inv);
     const uint32_t *m_nul = reinterpret_cast<const uint32_t *>(s_nul);
 #pragma unroll 2
     for (uint32_t a = 4 + (uint32_t)t; a + (uint32_t)k <= total; a += RC_PROBE_THREADS) {
-        const int mw = a >> 5, ms = a & 31;
-        const uint64_t nulw = (((uint64_t)m_nul[mw] << 32) | m_nul[mw + 1]) << ms;
-        if (nulw >> (64 - k)) continue;  // window crosses a read boundary (or padding)
-        const uint64_t invw = (((uint64_t)m_inv[mw] << 32) | m_inv[mw + 1]) << ms;
-        int cnt = 0;
-        if (!(invw >> (64 - k))) {
-            const int cw = a >> 4, cs = 2 * (a & 15);
-            uint64_t x = ((uint64_t)s_code[cw] << 32) | s_code[cw + 1];
-            if (cs) x = (x << cs) | ((uint64_t)s_code[cw + 2] >> (32 - cs));
-            cnt = rc_table_lookup<EXT>(T, rc_canonical(x >> (64 - 2 * k), k));
-        }
+        const rc_tile_win w = rc_tile_window(s_code, m_inv, m_nul, (int)a, k);
+        if (w.nul) continue;  // window crosses a read boundary (or padding)
+        const int cnt = w.bad ? 0 : rc_table_lookup<EXT>(T, rc_canonical(w.code, k));
         // the read this position belongs to: last j with lpos[j] <= a
         uint32_t lo = 0, hi = nr;
         while (hi - lo > 1) {
@@ -1322,6 +1263,13 @@ __global__ __launch_bounds__(RC_PROBE_THREADS) void k_probe_list(rc_table_view T
     }
 }
 
+// reads per workgroup of k_probe_list: a read takes its bases, the NUL and up to 6 bytes of alignment
+static uint32_t rc_probe_list_rpb(int max_len)
+{
+    const uint32_t rpb = (uint32_t)((RC_PROBE_TILE - 8) / (max_len + 8));
+    return rpb > RC_PLIST_MAX_READS ? RC_PLIST_MAX_READS : (rpb < 1 ? 1 : rpb);
+}
+
 int rc_launch_probe_list(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbytes, int32_t *d_counts, int skip_hi)
 {
     if (a.n == 0) return RC_OK;
@@ -1329,16 +1277,12 @@ int rc_launch_probe_list(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbyt
         rc_set_error(ctx, "probe: no k-mer table loaded");
         return RC_ERR_STATE;
     }
-    uint32_t rpb = (uint32_t)((RC_PROBE_TILE - 8) / (a.max_len + 8));  // a read takes its bases, the NUL and up to 6 bytes of alignment
-    if (rpb > RC_PLIST_MAX_READS) rpb = RC_PLIST_MAX_READS;
-    if (rpb < 1) rpb = 1;
+    const uint32_t rpb = rc_probe_list_rpb(a.max_len);
     rc_timer_begin(ctx);
-    if (ctx->ext)
-        hipLaunchKernelGGL(k_probe_list<true>, dim3((a.n + rpb - 1) / rpb), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), a.seq, nbytes, a.off,
-                           (const uint32_t *)ctx->loc_list.p, a.n, rpb, ctx->k, d_counts, a.mode, skip_hi, (const uint32_t *)nullptr);
-    else
-        hipLaunchKernelGGL(k_probe_list<false>, dim3((a.n + rpb - 1) / rpb), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), a.seq, nbytes, a.off,
-                           (const uint32_t *)ctx->loc_list.p, a.n, rpb, ctx->k, d_counts, a.mode, skip_hi, (const uint32_t *)nullptr);
+    rc_with_ext(ctx->ext, [&](auto ext) {
+        hipLaunchKernelGGL(k_probe_list<decltype(ext)::value>, dim3((a.n + rpb - 1) / rpb), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), a.seq, nbytes,
+                           a.off, (const uint32_t *)ctx->loc_list.p, a.n, rpb, ctx->k, d_counts, a.mode, skip_hi, (const uint32_t *)nullptr);
+    });
     rc_timer_end(ctx, RC_T_PROBE);
     RC_CHECK_HIP(ctx, hipGetLastError());
     return RC_OK;
@@ -1347,20 +1291,16 @@ int rc_launch_probe_list(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbyt
 int rc_launch_probe_tier(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbytes, int32_t *d_counts, int section)
 {
     if (a.n == 0) return RC_OK;
-    uint32_t rpb = (uint32_t)((RC_PROBE_TILE - 8) / (a.max_len + 8));
-    if (rpb > RC_PLIST_MAX_READS) rpb = RC_PLIST_MAX_READS;
-    if (rpb < 1) rpb = 1;
+    const uint32_t rpb = rc_probe_list_rpb(a.max_len);
     const uint32_t *list = (const uint32_t *)ctx->tier_list.p + (size_t)section * ctx->tier_stride;
     const uint32_t *n_list = (const uint32_t *)((char *)ctx->work.p + RC_WORK_NTIER_OFF) + section;
     unsigned grid = (a.n + rpb - 1) / rpb;  // (at most: the tier's share of the batch is not known here)
     if (grid > (unsigned)ctx->n_cu * 16u) grid = (unsigned)ctx->n_cu * 16u;
     rc_timer_begin(ctx);
-    if (ctx->ext)
-        hipLaunchKernelGGL(k_probe_list<true>, dim3(grid), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), a.seq, nbytes, a.off, list, a.n, rpb, ctx->k,
-                           d_counts, a.mode, -1, n_list);
-    else
-        hipLaunchKernelGGL(k_probe_list<false>, dim3(grid), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), a.seq, nbytes, a.off, list, a.n, rpb, ctx->k,
-                           d_counts, a.mode, -1, n_list);
+    rc_with_ext(ctx->ext, [&](auto ext) {
+        hipLaunchKernelGGL(k_probe_list<decltype(ext)::value>, dim3(grid), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), a.seq, nbytes, a.off, list,
+                           a.n, rpb, ctx->k, d_counts, a.mode, -1, n_list);
+    });
     rc_timer_end(ctx, RC_T_PROBE);
     RC_CHECK_HIP(ctx, hipGetLastError());
     return RC_OK;
@@ -1375,10 +1315,9 @@ int rc_launch_probe(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int32_t *d
     }
     const unsigned G = (unsigned)((nbytes + RC_PROBE_TILE - 1) / RC_PROBE_TILE);
     rc_timer_begin(ctx);
-    if (ctx->ext)
-        hipLaunchKernelGGL(k_probe<true>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq, nbytes, ctx->k, d_counts);
-    else
-        hipLaunchKernelGGL(k_probe<false>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq, nbytes, ctx->k, d_counts);
+    rc_with_ext(ctx->ext, [&](auto ext) {
+        hipLaunchKernelGGL(k_probe<decltype(ext)::value>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq, nbytes, ctx->k, d_counts);
+    });
     rc_timer_end(ctx, RC_T_PROBE);
     RC_CHECK_HIP(ctx, hipGetLastError());
     return RC_OK;

@@ -1,15 +1,14 @@
 // rc_weak.hip -- the per-read weak-k-mer profile (include/rcorrector_amd.h: rc_read_weak; arithmetic in rc_weak.h): which
 // k-windows of every read of an arena the table holds at least min_count times, reduced to four numbers per read.
 //
-// Two launches.  k_weak_planes probes every k-window of the arena as k_probe does (rc_table.hip: a 4 KiB tile + halo staged
-// into LDS as 2-bit codes and two bit masks, windows cut out with funnel shifts, one bucket probe per valid window) but keeps
-// one bit per window in two planes, solid and weak, instead of a count: a wavefront ballots 64 consecutive positions into one
+// Two launches.  k_weak_planes probes every k-window of the arena out of k_probe's tile (rc_device.h: rc_tile_stage; rc_common.h:
+// rc_tile_window; one bucket probe per valid window) but keeps one bit per window in two planes, solid and weak, instead of a
+// count: a wavefront ballots 64 consecutive positions into one
 // 64-bit word per plane, owns 1 KiB of the tile and so sixteen consecutive words of each plane, and writes them as one
 // 128-byte row -- 0.25 bytes per base against k_probe's 4.  k_weak_reduce then takes one read per lane: the (at most 17 for
 // 1 023 bases) words of each plane the read spans, through rc_weak_reduce.
-// The arena may start anywhere: it is read in aligned 16-byte pieces from the 16-byte boundary at or in front of its first
-// byte (`lead` bytes in front of it, and up to 15 behind its last, are read and masked to NULs), and the planes are
-// indexed by position + lead.
+// The arena may start anywhere: rc_tile_stage reads it from the 16-byte boundary at or in front of its first byte, `lead` bytes
+// in front of it, and the planes are indexed by position + lead.
 #include "rc_device.h"
 #include "rc_internal.h"
 #include "rc_weak.h"
@@ -27,31 +26,9 @@ __global__ __launch_bounds__(RC_PROBE_THREADS) void k_weak_planes(rc_table_view 
     __shared__ uint32_t s_code[RC_PROBE_TILE / 16 + 4];
     __shared__ uint16_t s_inv[RC_PROBE_TILE / 16 + 4];
     __shared__ uint16_t s_nul[RC_PROBE_TILE / 16 + 4];
-    const size_t tile0 = (size_t)blockIdx.x * RC_PROBE_TILE, end = (size_t)lead + nbytes;
+    const size_t tile0 = (size_t)blockIdx.x * RC_PROBE_TILE;
     const int t = threadIdx.x;
-
-    // stage: thread t packs bytes [16t, 16t+16) of the tile; threads 0..1 also pack the halo.  Bytes in front of the arena
-    // and behind it become NULs: no window reaches across them
-    for (int chunk = t; chunk < RC_PROBE_TILE / 16 + 2; chunk += RC_PROBE_THREADS) {
-        const size_t g = tile0 + (size_t)chunk * 16;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (g < end) {  // (an aligned piece that holds at least one byte of the arena, or lies between two that do)
-            v = *reinterpret_cast<const uint4 *>(seq16 + g);
-            if (g < lead || g + 16 > end) {
-                uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-                    if (g + j < lead || g + j >= end) w[j >> 2] &= ~(0xFFu << (8 * (j & 3)));
-                v = make_uint4(w[0], w[1], w[2], w[3]);
-            }
-        }
-        uint32_t code, inv, nul;
-        rc_pack16(v, code, inv, nul);
-        s_code[chunk] = code;
-        s_inv[chunk ^ 1] = (uint16_t)inv;  // big-endian bit order inside each 32-bit mask word
-        s_nul[chunk ^ 1] = (uint16_t)nul;
-    }
-    if (t < 2) s_code[RC_PROBE_TILE / 16 + 2 + t] = 0xFFFFFFFFu;
+    rc_tile_stage(seq16, lead, nbytes, tile0, s_code, s_inv, s_nul);
     __syncthreads();
     const uint32_t *m_inv = reinterpret_cast<const uint32_t *>(s_inv);
     const uint32_t *m_nul = reinterpret_cast<const uint32_t *>(s_nul);
@@ -63,18 +40,10 @@ __global__ __launch_bounds__(RC_PROBE_THREADS) void k_weak_planes(rc_table_view 
 #pragma unroll 2
     for (int it = 0; it < RC_WEAK_WAVE_WORDS; ++it) {
         const int a = wv * RC_WEAK_WAVE_BYTES + it * 64 + ln;
-        const int mw = a >> 5, ms = a & 31;
-        const uint64_t nulw = (((uint64_t)m_nul[mw] << 32) | m_nul[mw + 1]) << ms;
-        const uint64_t invw = (((uint64_t)m_inv[mw] << 32) | m_inv[mw + 1]) << ms;
+        const rc_tile_win w = rc_tile_window(s_code, m_inv, m_nul, a, k);
         // a window of k bytes, all of them ACGT, none a NUL (a read's end, or the arena's)
-        const bool valid = !(nulw >> (64 - k)) && !(invw >> (64 - k));
-        int cnt = 0;
-        if (valid) {
-            const int cw = a >> 4, cs = 2 * (a & 15);
-            uint64_t x = ((uint64_t)s_code[cw] << 32) | s_code[cw + 1];
-            if (cs) x = (x << cs) | ((uint64_t)s_code[cw + 2] >> (32 - cs));
-            cnt = rc_table_lookup<EXT>(T, rc_canonical(x >> (64 - 2 * k), k));
-        }
+        const bool valid = !w.nul && !w.bad;
+        const int cnt = valid ? rc_table_lookup<EXT>(T, rc_canonical(w.code, k)) : 0;
         const uint64_t bs = __ballot(valid && cnt >= min_count), bw = __ballot(valid && cnt < min_count);
         if (ln == it) {
             keep_s = bs;
@@ -110,14 +79,11 @@ int rc_launch_weak_planes(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int 
     const size_t plane_words = (size_t)(G ? G : 1) * (RC_PROBE_TILE / 64);
     if (const int rc = rc_dbuf_reserve(ctx, planes, plane_words * 16)) return rc;
     uint64_t *solid = (uint64_t *)planes->p, *weak = solid + plane_words;
-    if (G) {
-        if (ctx->ext)
-            hipLaunchKernelGGL(k_weak_planes<true>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq - lead, lead, nbytes, ctx->k,
-                               min_count, solid, weak);
-        else
-            hipLaunchKernelGGL(k_weak_planes<false>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq - lead, lead, nbytes, ctx->k,
-                               min_count, solid, weak);
-    }
+    if (G)
+        rc_with_ext(ctx->ext, [&](auto ext) {
+            hipLaunchKernelGGL(k_weak_planes<decltype(ext)::value>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq - lead, lead, nbytes,
+                               ctx->k, min_count, solid, weak);
+        });
     *solid_out = solid;
     *weak_out = weak;
     *lead_out = lead;

@@ -39,6 +39,19 @@ def test_pack16m_swar_equals_its_definition(tmp_path):
     assert p.returncode == 0 and out.startswith("ok "), out
 
 
+def test_tile_window_equals_a_loop_over_the_bytes(tmp_path):
+    """rc_tile_window (what k_probe, k_probe_list, k_count_scan and k_weak_planes cut a position's k-mer out of the staged tile
+    with: crosses a NUL / holds a letter outside ACGT / the 2k-bit code) against a loop over the bytes, on planes built from the
+    packer's per-byte definition: every k in 4 .. 32 at every position of 128 bytes + halo + sentinels; letters only, a NUL / an N
+    / a lower-case letter at each single position, a NUL and an N exactly k apart.  Any mismatch fails."""
+    exe = str(tmp_path / "tile_window")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "rcorrector_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "hostmath", "tile_window.cpp"), "-o", exe], check=True)
+    p = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    out = p.stdout.decode()
+    assert p.returncode == 0 and out.startswith("ok "), out
+
+
 def test_kmer_walk_reciprocal_is_exact():
     """The fused probe kernel's k-mer walk (rc_correct.hip: tiles whose reads all have K k-mers) maps k-mer v to read v / K by one
     multiply-high with floor(2^32 / K) + 1: exact for every K a read of up to 160 bases can have and every v a tile can hold
