@@ -611,6 +611,16 @@ int rc_profile_reset(rc_ctx *ctx);
  * host's bit for bit. */
 int rc_selftest_get_bound(rc_ctx *ctx, const int32_t *c, size_t n, double error_rate, int32_t *out_int, double *out_dbl);
 
+/* test support: how the last batch this context ran through rc_correct_device or rc_correct_batch was routed.  Waits for the
+ * context's stream and copies, for each of its n reads: cls (0 = finished before the general correction kernel, else that
+ * kernel's work class 1..4), cand (> 0 = the threshold kernel offered the read to the isolated-substitution kernel: the number
+ * of its untrusted stretches) and runs (candidates only; low 32 bits: stretch 0 | stretch 1 << 16, next 16 bits: stretch 2, top
+ * 16 bits: the number of stretches; a stretch = first k-mer | length << 8).  cls == 0 && cand == 0: finished by the threshold
+ * kernel; cls == 0 && cand > 0: by the isolated-substitution kernel; cls != 0: by the general kernel.  Launches nothing.
+ * RC_ERR_STATE (the text says which) when the arrays do not describe the whole batch: none has run, it failed, it ran in length tiers (a
+ * read of more than 160 bases), without classification or without candidates, or n is not its number of reads. */
+int rc_debug_routes(rc_ctx *ctx, uint8_t *cls_out, uint8_t *cand_out, uint64_t *runs_out, uint32_t n);
+
 /* summary counters, struct _summary main.cpp:32-36,73-79: reads and corrected bases of every batch
  * this context has corrected through any entry point (accumulated on the device; waits for the
  * context's kernels) */

@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
     "rc_pack_bases", "rc_submit_packed", "rc_wait_packed", "rc_apply_fixes",
-    "rc_profile_enable", "rc_profile_get", "rc_profile_reset", "rc_profile_correct_counters", "rc_profile_read_rounds", "rc_selftest_get_bound", "rc_summary",
+    "rc_profile_enable", "rc_profile_get", "rc_profile_reset", "rc_profile_correct_counters", "rc_profile_read_rounds", "rc_selftest_get_bound", "rc_debug_routes", "rc_summary",
 ]
 
 
@@ -234,6 +234,7 @@ def load_library():
     L.rc_profile_correct_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rc_profile_read_rounds.argtypes = [vp, vp]
     L.rc_selftest_get_bound.argtypes = [vp, vp, sz, C.c_double, vp, vp]
+    L.rc_debug_routes.argtypes = [vp, vp, vp, vp, C.c_uint32]
     L.rc_summary.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
@@ -826,6 +827,13 @@ class Context:
         od = np.zeros(len(c), dtype=np.float64)
         self._ck(self._L.rc_selftest_get_bound(self._h, c.ctypes.data, len(c), error_rate, oi.ctypes.data, od.ctypes.data))
         return oi, od
+
+    def debug_routes(self, n):
+        """Test support (rc_debug_routes): (cls uint8[n], cand uint8[n], runs uint64[n]) of the last batch correct_batch /
+        correct_device ran -- which kernel finished each read.  Raises where the arrays do not describe the whole batch."""
+        cls, cand, runs = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint64)
+        self._ck(self._L.rc_debug_routes(self._h, cls.ctypes.data, cand.ctypes.data, runs.ctypes.data, n))
+        return cls, cand, runs
 
     def summary(self):
         a, b = C.c_uint64(0), C.c_uint64(0)

@@ -406,6 +406,41 @@ int rc_selftest_get_bound(rc_ctx *ctx, const int32_t *c, size_t n, double error_
     return RC_OK;
 }
 
+// test support: which kernel finished each read of the batch this context ran last -- cls (0: finished before k_correct; k_single
+// clears it, rc_single.h), cand (the threshold kernel's flag for k_single: the number of stretches) and runs (the stretches, x in
+// the low word) as they lie in HBM.  Copies only: no kernel is launched, and the correction kernels know nothing of it.
+// (rc_correct_batch is slot 0, which runs in the context itself -- rc_slot_lane -- so these are the buffers it wrote.)
+int rc_debug_routes(rc_ctx *ctx, uint8_t *cls_out, uint8_t *cand_out, uint64_t *runs_out, uint32_t n)
+{
+    if (!ctx || !cls_out || !cand_out || !runs_out) return RC_ERR_ARG;
+    const char *why = nullptr;
+    if (ctx->routes_state == rc_ctx::RC_ROUTES_NONE)
+        why = "no batch has run in this context";
+    else if (ctx->routes_state == rc_ctx::RC_ROUTES_FAILED)
+        why = "the last batch did not run to its end";
+    else if (ctx->routes_state == rc_ctx::RC_ROUTES_TIERED)
+        why = "the last batch ran in length tiers (a read of more than 160 bases): the arrays are rewritten per pass";
+    else if (!ctx->cls_ready)
+        why = "the last batch ran without classification (cls_ready is false)";
+    else if (!ctx->cand_ready)
+        why = "the last batch ran without k_single's candidates (cand_ready is false)";
+    if (why) {
+        rc_set_error(ctx, "debug_routes: %s", why);
+        return RC_ERR_STATE;
+    }
+    if (n != ctx->routes_n) {
+        rc_set_error(ctx, "debug_routes: n = %u, the last batch had %u reads", n, ctx->routes_n);
+        return RC_ERR_STATE;
+    }
+    if (n == 0) return RC_OK;
+    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RC_CHECK_HIP(ctx, hipMemcpy(cls_out, ctx->cls.p, n, hipMemcpyDeviceToHost));
+    RC_CHECK_HIP(ctx, hipMemcpy(cand_out, ctx->cand.p, n, hipMemcpyDeviceToHost));
+    RC_CHECK_HIP(ctx, hipMemcpy(runs_out, ctx->runs.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    return RC_OK;
+}
+
 int rc_summary(const rc_ctx *c, uint64_t *total_reads, uint64_t *total_corrections)
 {
     if (!c) return RC_ERR_ARG;

@@ -54,6 +54,7 @@ int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_
 {
     int rc;
     bool fused = false;  // probe and threshold kernels ran as one
+    ctx->routes_state = rc_ctx::RC_ROUTES_FAILED;  // (rc_debug_routes: until the batch has run to its end, cls / cand / runs describe nothing)
     if ((rc = rc_dbuf_reserve(ctx, &ctx->counts, (size_t)b->nbytes * 4 + 256))) return rc;
     if ((rc = rc_dbuf_reserve(ctx, &ctx->strong, (size_t)b->n_reads * 4 + 256))) return rc;
     if ((rc = rc_dbuf_reserve(ctx, &ctx->info, (size_t)b->n_reads * 4 + 256))) return rc;
@@ -151,7 +152,9 @@ int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_
             if ((rc = single_and_compact(at))) return rc;
             if ((rc = rc_launch_correct(ctx, at))) return rc;
         }
-        return rc_launch_summary(ctx, a.ret, a.n);
+        if ((rc = rc_launch_summary(ctx, a.ret, a.n))) return rc;
+        ctx->routes_state = rc_ctx::RC_ROUTES_TIERED;
+        return RC_OK;
     }
     if (locality) {
         if ((rc = rc_launch_locality_order(ctx, a, (size_t)b->nbytes))) return rc;
@@ -177,7 +180,10 @@ int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_
     if ((rc = single_and_compact(a))) return rc;
     if ((rc = rc_launch_correct(ctx, a))) return rc;
     // UpdateSummary (main.cpp:73-79), on the device: the counters live in HBM until rc_summary() asks
-    return rc_launch_summary(ctx, a.ret, a.n);
+    if ((rc = rc_launch_summary(ctx, a.ret, a.n))) return rc;
+    ctx->routes_state = rc_ctx::RC_ROUTES_WHOLE;
+    ctx->routes_n = a.n;
+    return RC_OK;
 }
 
 // GetStrongTrustedThreshold (ErrorCorrection.h:26, ErrorCorrection.cpp:1482-1565) for every read of

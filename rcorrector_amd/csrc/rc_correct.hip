@@ -546,7 +546,7 @@ int rc_launch_threshold(rc_ctx *ctx, const rc_device_batch_args &a, bool classif
         if ((rc = rc_dbuf_reserve(ctx, &ctx->cls, (size_t)a.n + 256))) return rc;
         A.cls = (uint8_t *)ctx->cls.p;
         ctx->cls_ready = true;
-        if (quarter && !ctx->env_no_single && ec) {  // candidates of k_single (rc_single.h)
+        if (quarter && ec) {  // candidates of k_single (rc_single.h; under RC_NO_SINGLE too: flagged, not taken)
             if ((rc = rc_dbuf_reserve(ctx, &ctx->cand, (size_t)a.n + 256))) return rc;
             if ((rc = rc_dbuf_reserve(ctx, &ctx->runs, (size_t)a.n * 8 + 256))) return rc;
             A.cand = (uint8_t *)ctx->cand.p;
@@ -598,13 +598,12 @@ int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, s
         if ((rc = rc_dbuf_reserve(ctx, &ctx->cls, (size_t)a.n + 256))) return rc;
         A.cls = (uint8_t *)ctx->cls.p;
         ctx->cls_ready = true;
-        if (!ctx->env_no_single) {  // candidates of k_single (rc_single.h)
-            if ((rc = rc_dbuf_reserve(ctx, &ctx->cand, (size_t)a.n + 256))) return rc;
-            if ((rc = rc_dbuf_reserve(ctx, &ctx->runs, (size_t)a.n * 8 + 256))) return rc;
-            A.cand = (uint8_t *)ctx->cand.p;
-            A.runs = (uint2 *)ctx->runs.p;
-            ctx->cand_ready = true;
-        }
+        // candidates of k_single (rc_single.h; under RC_NO_SINGLE too: flagged, not taken)
+        if ((rc = rc_dbuf_reserve(ctx, &ctx->cand, (size_t)a.n + 256))) return rc;
+        if ((rc = rc_dbuf_reserve(ctx, &ctx->runs, (size_t)a.n * 8 + 256))) return rc;
+        A.cand = (uint8_t *)ctx->cand.p;
+        A.runs = (uint2 *)ctx->runs.p;
+        ctx->cand_ready = true;
     }
     // reads per workgroup: a read takes its bases, the NUL and up to 6 bytes of alignment; whole passes
     // of the 16-row threshold code (mates stay together); the small arena unless the large one holds

@@ -242,10 +242,15 @@ struct rc_ctx {
     int env_force_ec = 0;      // RC_FORCE_EC=9|10 (dev / tests): at least this many count registers per lane in the 160-base instances
     bool env_no_tier = false;  // RC_NO_TIER=1 (dev / tests): no length tiers, the longest read of a batch decides every kernel
     bool env_k3_generic = false;  // RC_K3_GENERIC=1 (dev / tests): the any-k instance of k_correct even where a compiled-for-k one exists
-    bool env_no_single = false;  // RC_NO_SINGLE=1 (dev / tests): no isolated-substitution kernel, every listed read goes to k_correct
+    bool env_no_single = false;  // RC_NO_SINGLE=1 (dev / tests): k_single is not launched (rc_launch_single) -- every listed read goes to k_correct; the
+                                 // threshold kernel flags its candidates all the same, and rc_debug_routes shows which reads it would have been offered
     bool env_no_alt = false;  // RC_NO_ALT=1 (dev / tests): rc_run_params::flags |= RC_PF_NO_ALT
     int locality_mode = 0;  // 0: large batches over large tables, 1: always (RC_LOCALITY=force), -1: never (RC_LOCALITY=off)
     bool cls_ready = false;  // cls / worklist describe this batch
+    // what rc_debug_routes (test support) may say of cls / cand / runs: the batch rc_correct_device_impl ran last in this context
+    enum { RC_ROUTES_NONE, RC_ROUTES_FAILED, RC_ROUTES_TIERED, RC_ROUTES_WHOLE } routes_state = RC_ROUTES_NONE;  // (FAILED: also while one runs;
+                                                                                                                // TIERED: the arrays are rewritten per pass)
+    uint32_t routes_n = 0;  // the batch's reads (RC_ROUTES_WHOLE)
     size_t work_stride = 0;  // uint32 entries between the sections of worklist
     // getenv() results, read once at rc_create
     bool env_k2_wave_per_read = false, env_no_classify = false, env_timing = false;

@@ -37,7 +37,9 @@
 // each fix replaced by the counts the path just fetched (the k-th window, which a right search never visits, is
 // fetched for this purpose).  tests: every GPU parity set and fuzz seed runs with this kernel in the path;
 // RC_NO_SINGLE=1 takes it out (knob matrix); a Python restatement of the same conditions was checked against the
-// oracle on every data set first.
+// oracle on every data set first.  The acceptance set itself -- which reads this kernel finishes, which the
+// threshold kernel flags for it and with which stretches -- is pinned against that restatement read by read, in both directions,
+// by tests/test_routing.py (through rc_debug_routes, rc_api.hip).
 #pragma once
 
 #ifndef RC_K2S_WAVES

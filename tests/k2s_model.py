@@ -3,8 +3,10 @@ the general search (rcorrector_amd/csrc/rc_quarter.h: the clean test on the real
 of k_single) -- the model those kernels were written from.  `finished_early` returns None when the read has to go
 through the search, else (ret, corrected read, l, m, h): what ErrorCorrection + GetKmerInformation
 (ErrorCorrection.cpp:682-1480, :1567-1602) must produce for it.  tests/test_k2s_model.py checks exactly that against
-the oracle.  `allow_double` adds "class D" (two substitutions less than k bases apart inside the read; DESIGN.md
-section 3: validated here, not built on the device).  Test infrastructure: nothing in the product imports this."""
+the oracle.  `shape` is the part of it the threshold kernel decides -- conditions (0)-(2), the untrusted stretches it
+hands to k_single -- and tests/test_routing.py holds the device kernels' routing to both on the GPU.  `allow_double` adds
+"class D" (two substitutions less than k bases apart inside the read; DESIGN.md section 3: validated here, not built on
+the device).  Test infrastructure: nothing in the product imports this."""
 import ctypes as C
 
 import numpy as np
@@ -35,12 +37,10 @@ def polya(seq, k, thr):
     cA = np.concatenate([[0], np.cumsum(a == 65)]); cT = np.concatenate([[0], np.cumsum(a == 84)])
     na = cA[k:] - cA[:-k]; nt = cT[k:] - cT[:-k]
     return (na >= k - thr) | (nt >= k - thr)
-def finished_early(P, T, seq, k, mfk, strong0, info0, pair_t, allow_double=False, max_fix=3):
-    Ln = len(seq)
-    if Ln < k or (info0 & 4): return None
-    if any(ch not in b"ACGT" for ch in seq): return None
-    kc = Ln - k + 1
-    counts = po.kmer_counts(P, T, seq).astype(np.int64)
+
+
+def first_thresholds(P, strong0, info0, pair_t):
+    """(s, t): the strong and the weak threshold of ErrorCorrection's first iteration (ErrorCorrection.cpp:793-842)"""
     strong = strong0; flag = False
     trust = bound_i(P, strong)
     if info0 & 1:
@@ -49,33 +49,62 @@ def finished_early(P, T, seq, k, mfk, strong0, info0, pair_t, allow_double=False
         if (not flag) or pair_t < 20: trust = bound_i(P, pair_t)
         strong = pair_t
     if trust < 2: trust = 2
-    t = trust
+    return strong, trust
+
+
+def shape(P, T, seq, k, mfk, strong0, info0, pair_t, allow_double=False, max_fix=3):
+    """Conditions (0)-(2): what the threshold kernel decides.  None: the read is screened, shorter than k or has a letter outside
+    ACGT.  Else a dict: counts, s / t (the first iteration's thresholds, ErrorCorrection.cpp:793-842, pair override included),
+    pa2 (IsPolyA at 2 per window), clean (condition (0)), segs (the untrusted stretches (z0, z1, kind) where the trusted mask
+    has the shape of condition (2), whatever their number; None where it has not) and ok: not clean, segs, and at most
+    min(max_fix, mfk - 1) fixes -- the whole of condition (2)."""
+    Ln = len(seq)
+    if Ln < k or (info0 & 4): return None
+    if any(ch not in b"ACGT" for ch in seq): return None
+    kc = Ln - k + 1
+    counts = po.kmer_counts(P, T, seq).astype(np.int64)
+    strong, t = first_thresholds(P, strong0, info0, pair_t)
     pa2 = polya(seq, k, 2)
     Tm = (counts >= strong) & ~pa2
+    out = dict(counts=counts, s=strong, t=t, pa2=pa2, kc=kc, clean=False, segs=None, ok=False)
     if counts.min() >= t and bool((Tm[:-1] & Tm[1:]).any()):     # condition (0): nothing to correct -- a real island (two
         # adjacent trusted k-mers, ErrorCorrection.cpp:870-931) and no count below the weak threshold
-        v = np.sort(np.where(counts == 0, 1, counts))
-        return 0, bytes(seq), int(v[0]), int(v[len(v) // 2]), int(v[-1])
+        out["clean"] = True
+        return out
     d_ = np.diff(np.concatenate([[0], Tm.astype(np.int8), [0]]))
     starts = np.nonzero(d_ == 1)[0]; ends = np.nonzero(d_ == -1)[0] - 1
-    if len(starts) < 1: return None
-    if ((ends - starts + 1) < 2).any(): return None
+    if len(starts) < 1: return out
+    if ((ends - starts + 1) < 2).any(): return out
     segs = []   # (z0, z1, kind)
     if starts[0] > 0:
-        if starts[0] > k: return None
+        if starts[0] > k: return out
         segs.append((0, int(starts[0]) - 1, 'L'))
     for i in range(len(starts) - 1):
         z0, z1 = int(ends[i]) + 1, int(starts[i + 1]) - 1
         zl = z1 - z0 + 1
         if zl == k: segs.append((z0, z1, 'M'))
         elif allow_double and k < zl <= 2 * k - 1: segs.append((z0, z1, 'D'))
-        else: return None
+        else: return out
     if ends[-1] < kc - 1:
         z0 = int(ends[-1]) + 1
-        if kc - z0 > k: return None
+        if kc - z0 > k: return out
         segs.append((z0, kc - 1, 'R'))
+    out["segs"] = segs
     nfix = sum(2 if s[2] == 'D' else 1 for s in segs)
-    if not segs or nfix > min(max_fix, mfk - 1): return None
+    out["nfix"] = nfix
+    out["ok"] = bool(segs) and nfix <= min(max_fix, mfk - 1)
+    return out
+
+
+def finished_early(P, T, seq, k, mfk, strong0, info0, pair_t, allow_double=False, max_fix=3):
+    sh = shape(P, T, seq, k, mfk, strong0, info0, pair_t, allow_double, max_fix)
+    if sh is None: return None
+    counts, strong, t, pa2, kc = sh["counts"], sh["s"], sh["t"], sh["pa2"], sh["kc"]
+    if sh["clean"]:
+        v = np.sort(np.where(counts == 0, 1, counts))
+        return 0, bytes(seq), int(v[0]), int(v[len(v) // 2]), int(v[-1])
+    if not sh["ok"]: return None
+    segs, nfix = sh["segs"], sh["nfix"]
     cur = bytearray(seq)          # the read with the fixes made so far
     newcounts = counts.copy()
     best_bott = 10**9
