@@ -372,6 +372,74 @@ int rc_trust_profile_begin(rc_ctx *ctx, int32_t min_count);
 int rc_trust_profile_get(rc_ctx *ctx, rc_trust_profile *out);
 int rc_trust_profile_end(rc_ctx *ctx);
 
+/* ---- mate-overlap report: where the two mates of a pair disagree, before and after correction ------------------------------
+ * Evidence that does not come from the k-mer table: where a fragment is shorter than its two reads together, mate 1 and the
+ * reverse complement of mate 2 cover some bases twice, and a base they disagree on is a sequencing error in one of them.
+ * A PAIR is (a, b), mate 1 of La bytes and mate 2 of Lb bytes; mode 1: read r of the first half of the reads with read r of the
+ * second half, mode 2: reads 2u and 2u + 1 (the mates of the duplicate census); mode 0 has no pairs.  A base is VALID if it is
+ * upper-case A, C, G or T.  r is the reverse complement of b: r[j] = comp(b[Lb - 1 - j]), A <-> T, C <-> G, any other byte
+ * invalid.  For an OFFSET d in [-(Lb - 1), La - 1], a[i] faces r[i - d] for i in [max(0, d), min(La, d + Lb)); v(d) is the number
+ * of faced positions where both bases are valid, m(d) the number of those where they differ.  d is ACCEPTED if
+ * v(d) >= min_overlap and 100 m(d) <= max_mismatch_pct v(d) (integers).  The CHOSEN offset d* is the accepted one with the
+ * largest v, then the smallest m, then the smallest d.  d* is decided on the bases as they arrived and applied unchanged to the
+ * corrected bases (corrections are substitutions: the lengths are equal).  A pair without an accepted offset is not
+ * overlapping and adds to `pairs` alone.  The fragment length is F = d* + Lb; d* < 0 is read-through.  Of a mate longer than
+ * 1023 bases (the reference's reads hold no more, utils.h:7) the first 1023 are looked at.
+ *   pairs, overlapping
+ *   compared_x, disagree_x     the sums of v and m at d*, in version x
+ *   resolved                   positions valid-and-different before, valid-and-equal after
+ *   introduced                 positions valid-and-equal before, valid-and-different after: probable miscorrections
+ *   kept                       positions that differ in both versions (one whose validity changes is in none of the three)
+ *   pairs_improved / _worsened / _same   overlapping pairs with m after below / above / equal to m before
+ *   frag[F]                    overlapping pairs by fragment length, F in 1 .. 2046
+ *   compared5[mate][p], disagree5_before[mate][p], disagree5_after[mate][p]   by position from the 5' end of that mate: mate 1
+ *                              p = i, mate 2 p = Lb - 1 - (i - d*), its index in b; compared5 counts the positions valid before
+ * so sum(frag) == overlapping == pairs_improved + pairs_worsened + pairs_same, sum(compared5[0]) == sum(compared5[1]) ==
+ * compared_before, sum(disagree5_x[0]) == sum(disagree5_x[1]) == disagree_x, and disagree_before == resolved + kept + (the
+ * positions that differ before and are invalid after).  A low-complexity pair (a homopolymer, a short repeat) may be given an
+ * offset that is not its fragment's; min_overlap 30 and max_mismatch_pct 10 keep that rare.
+ * While a session is open on a context, every batch of pairs that completes on it -- rc_correct_batch, rc_correct_batch_traced,
+ * rc_wait, rc_wait_packed, rc_wait_resident (the batches of slots that run in lanes included) and rc_correct_device (in
+ * stream order, at the end of the call) -- counts once, its bases as they were in HBM in front of the first correction kernel
+ * (one copy of the arena, shared with the correction report where both are open) against its bases as corrected.  A packed or
+ * resident batch that came back with RC_STATUS_NOSPACE counts when its resubmission completes; a single-end batch (mode 0) adds
+ * nothing.  No session open, those calls launch, copy and allocate nothing for it; open or not, the corrected reads, ret / l /
+ * m / h, rc_summary and rc_table_digest are the same.  Needs no table.
+ * begin: RC_STATUS_STATE if open already, RC_STATUS_ARG: min_overlap outside 1 .. 1023, max_mismatch_pct outside 0 .. 50.  get:
+ * waits for what is outstanding on the context and its lanes, then copies the counts out; the session stays open and goes on
+ * accumulating; RC_STATUS_STATE if not open, RC_STATUS_ARG: out == NULL.  end: closes and frees (rc_destroy does too);
+ * RC_STATUS_STATE if not open; a batch in flight across end is in no session.  While a session is open rc_correct_device BLOCKS
+ * until the batch's counts are in the session.  Threads: as for the trust profile (the lanes add under a mutex).  Open, the
+ * kernel reads the arena in aligned 16-byte pieces: rc_correct_device's d_seq is read (never written) up to 15 bytes in front
+ * of its first and behind its last byte, within the 16-byte granules those bytes lie in.  No reference counterpart. */
+#define RC_OVERLAP_MAX_LEN 1024
+#define RC_OVERLAP_FRAG_LEN 2048
+typedef struct {
+    uint64_t min_overlap, max_mismatch_pct; /* the session's (rc_mate_overlap_get); rc_mate_overlap_device leaves them alone */
+    uint64_t pairs, overlapping;
+    uint64_t compared_before, disagree_before, compared_after, disagree_after;
+    uint64_t resolved, introduced, kept;
+    uint64_t pairs_improved, pairs_worsened, pairs_same;
+    uint64_t frag[RC_OVERLAP_FRAG_LEN];
+    uint64_t compared5[2][RC_OVERLAP_MAX_LEN], disagree5_before[2][RC_OVERLAP_MAX_LEN], disagree5_after[2][RC_OVERLAP_MAX_LEN];
+} rc_mate_overlap;
+/* The pairs of two arenas in HBM that share one offset array: n_reads reads, read r the NUL-terminated string at d_off[r] of
+ * d_before (the bases as read) and of d_after (as corrected), d_off has n_reads + 1 entries; their counts are ADDED to
+ * *d_counts, an rc_mate_overlap in HBM that the caller zeroed (or that holds earlier arenas' counts).  d_before == d_after is
+ * allowed: nothing was corrected, every after figure equals its before figure.  Asynchronous on the context's stream
+ * (rc_sync() to wait); needs neither a table nor an open session.  Neither arena is written; both may be read in aligned 16-byte
+ * pieces up to 15 bytes in front of their first and behind their last byte.  max_read_len, the longest read in bases, picks
+ * the kernel instance (up to 256 bases, or up to 1023); the kernel cuts every mate to what its instance holds, so a wrong
+ * max_read_len can never index outside the arrays -- a mate longer than it said merely has only its first bases looked at.
+ * RC_STATUS_ARG: a mode outside 1 .. 2, an odd n_reads, min_overlap outside 1 .. 1023, max_mismatch_pct outside 0 .. 50,
+ * nbytes >= 2^32, a null pointer with n_reads > 0.  No reference counterpart. */
+int rc_mate_overlap_device(rc_ctx *ctx, const uint8_t *d_before, const uint8_t *d_after, const uint32_t *d_off, uint32_t n_reads,
+                           uint64_t nbytes, int32_t max_read_len, int32_t mode, int32_t min_overlap, int32_t max_mismatch_pct,
+                           rc_mate_overlap *d_counts);
+int rc_mate_overlap_begin(rc_ctx *ctx, int32_t min_overlap, int32_t max_mismatch_pct);
+int rc_mate_overlap_get(rc_ctx *ctx, rc_mate_overlap *out);
+int rc_mate_overlap_end(rc_ctx *ctx);
+
 /* ---- run parameters (globals of main.cpp:17-30) ----------------------------------------------- */
 /* replaces main.cpp:310-358 (ERROR_RATE estimation).  Uses the entries parsed by the last
  * rc_table_load_jfdump() in file order -- or, for a table that was counted here or built from

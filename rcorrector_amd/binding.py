@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "rc_weak_profile_device", "rc_weak_profile_into",
     "rc_dup_census_begin", "rc_dup_census_get", "rc_dup_census_end", "rc_read_keys_device", "rc_dup_census_merge",
     "rc_trust_profile_device", "rc_trust_profile_begin", "rc_trust_profile_get", "rc_trust_profile_end",
+    "rc_mate_overlap_device", "rc_mate_overlap_begin", "rc_mate_overlap_get", "rc_mate_overlap_end",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
@@ -116,6 +117,35 @@ class _TrustProfile(C.Structure):
     _fields_ = [("k", C.c_int32), ("min_count", C.c_int32), ("reads", C.c_uint64 * 2), ("before", _TrustCounts), ("after", _TrustCounts)]
 
 
+OVERLAP_MAX_LEN = 1024
+OVERLAP_FRAG_LEN = 2048
+OVERLAP_SCALARS = ("min_overlap", "max_mismatch_pct", "pairs", "overlapping", "compared_before", "disagree_before", "compared_after", "disagree_after",
+                   "resolved", "introduced", "kept", "pairs_improved", "pairs_worsened", "pairs_same")
+OVERLAP_ARRAYS = ("frag", "compared5", "disagree5_before", "disagree5_after")
+OVERLAP_WORDS = len(OVERLAP_SCALARS) + OVERLAP_FRAG_LEN + 6 * OVERLAP_MAX_LEN
+
+
+class _MateOverlap(C.Structure):
+    """rc_mate_overlap: 64-bit counts throughout"""
+    _fields_ = ([(n, C.c_uint64) for n in OVERLAP_SCALARS] + [("frag", C.c_uint64 * OVERLAP_FRAG_LEN)] +
+                [(n, (C.c_uint64 * OVERLAP_MAX_LEN) * 2) for n in OVERLAP_ARRAYS[1:]])
+
+
+def mate_overlap_dict(words):
+    """OVERLAP_WORDS 64-bit words laid out as an rc_mate_overlap (a copy of device memory, say) -> the dict Context.mate_overlap returns"""
+    w = np.ascontiguousarray(words).reshape(-1).view(np.uint64)
+    if w.size != OVERLAP_WORDS:
+        raise ValueError("an rc_mate_overlap has %d 64-bit words, got %d" % (OVERLAP_WORDS, w.size))
+    out = {n: int(w[i]) for i, n in enumerate(OVERLAP_SCALARS)}
+    at = len(OVERLAP_SCALARS)
+    out["frag"] = w[at:at + OVERLAP_FRAG_LEN].copy()
+    at += OVERLAP_FRAG_LEN
+    for n in OVERLAP_ARRAYS[1:]:
+        out[n] = w[at:at + 2 * OVERLAP_MAX_LEN].reshape(2, OVERLAP_MAX_LEN).copy()
+        at += 2 * OVERLAP_MAX_LEN
+    return out
+
+
 class _DeviceBatch(C.Structure):
     _fields_ = [("mode", C.c_int), ("n_reads", C.c_uint32), ("nbytes", C.c_uint64),
                 ("max_read_len", C.c_int32),
@@ -203,6 +233,10 @@ def load_library():
     L.rc_trust_profile_begin.argtypes = [vp, C.c_int32]
     L.rc_trust_profile_get.argtypes = [vp, C.POINTER(_TrustProfile)]
     L.rc_trust_profile_end.argtypes = [vp]
+    L.rc_mate_overlap_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
+    L.rc_mate_overlap_begin.argtypes = [vp, C.c_int32, C.c_int32]
+    L.rc_mate_overlap_get.argtypes = [vp, C.POINTER(_MateOverlap)]
+    L.rc_mate_overlap_end.argtypes = [vp]
     L.rc_estimate_error_rate.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
     L.rc_bad_quality_from_hist.restype = C.c_char
     L.rc_bad_quality_from_hist.argtypes = [vp, vp, C.c_int32]
@@ -546,6 +580,32 @@ class Context:
     def trust_profile_end(self):
         """rc_trust_profile_end: closes the profile and frees its counts and scratch."""
         self._ck(self._L.rc_trust_profile_end(self._h))
+
+    # ---- mate-overlap report: where the mates of a pair disagree, before and after correction ----
+    def mate_overlap_begin(self, min_overlap=30, max_mismatch_pct=10):
+        """rc_mate_overlap_begin: from now on every batch of pairs that completes on this context (any batch entry point, slot
+        lanes included) is counted once: mate 1 against the reverse complement of mate 2 at the offset chosen on the bases as
+        they arrived, before and after correction.  Needs no table."""
+        self._ck(self._L.rc_mate_overlap_begin(self._h, int(min_overlap), int(max_mismatch_pct)))
+
+    def mate_overlap(self):
+        """rc_mate_overlap_get: a dict named as the struct's fields -- ints ("min_overlap", "max_mismatch_pct", "pairs",
+        "overlapping", "compared_before", ...) and uint64 arrays: "frag" (RC_OVERLAP_FRAG_LEN), "compared5", "disagree5_before",
+        "disagree5_after" (2, RC_OVERLAP_MAX_LEN): [mate][position].  The session stays open."""
+        r = _MateOverlap()
+        self._ck(self._L.rc_mate_overlap_get(self._h, C.byref(r)))
+        return mate_overlap_dict(np.frombuffer(bytes(r), np.uint64))
+
+    def mate_overlap_end(self):
+        """rc_mate_overlap_end: closes the session and frees its counts."""
+        self._ck(self._L.rc_mate_overlap_end(self._h))
+
+    def mate_overlap_device(self, d_before, d_after, d_off, n_reads, nbytes, max_read_len, mode, d_counts, min_overlap=30, max_mismatch_pct=10):
+        """rc_mate_overlap_device: the pairs of two arenas in HBM that share d_off, the bases as read and as corrected (may be
+        one and the same), ADDED to d_counts: device memory for one rc_mate_overlap (OVERLAP_WORDS uint64, zeroed by the caller;
+        mate_overlap_dict reads a copy of it).  Asynchronous on the context's stream."""
+        self._ck(self._L.rc_mate_overlap_device(self._h, _ptr(d_before), _ptr(d_after), _ptr(d_off), n_reads, nbytes, int(max_read_len), int(mode),
+                                                int(min_overlap), int(max_mismatch_pct), _ptr(d_counts)))
 
     def trust_profile_device(self, d_seq, d_off, n_reads, nbytes, max_read_len, mode, d_counts, min_count=1):
         """rc_trust_profile_device: the reads of an arena in HBM as they are, ADDED to d_counts: device memory for one

@@ -287,7 +287,7 @@ int rc_correct_read(rc_ctx *ctx, char *seq, const char *qual, int32_t pair_stron
     if (rc) return rc;
     a.pair_override = pair_strong_threshold;
     const uint8_t *snap;  // (the correction report alone: one read is no batch of the run for the other observers)
-    if ((rc = rc_report_snapshot(ctx, a.seq, n1, &snap))) return rc;
+    if ((rc = rc_report_snapshot(ctx, a.seq, n1, false, &snap))) return rc;
     if ((rc = rc_launch_probe(ctx, a.seq, n1, (int32_t *)ctx->counts.p))) return rc;
     // no threshold kernel, no classification: k_correct computes the read's own threshold (its single-end front end) and
     // takes the pair's from the argument, exactly the reference's call

@@ -124,8 +124,8 @@ extern "C" {  // (defined inside the units' extern "C" blocks)
 // of d_qual; qual_bits: -1 = as rc_set_quality_bits says, 0 / 1 = this batch's quality arena holds bytes / bits (the packed boundary)
 int rc_correct_check(rc_ctx *ctx, const rc_device_batch *b);
 int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits);
-// rc_api_observe.hip -- the one place the batch observers (correction report, duplicate census, trust profile, recount
-// follow) are hooked in.  ctx is the context the batch runs in (a context or one of its slot lanes).
+// rc_api_observe.hip -- the one place the batch observers (correction report, duplicate census, trust profile, mate-overlap
+// report, recount follow) are hooked in.  ctx is the context the batch runs in (a context or one of its slot lanes).
 // rc_correct_observed: what every batch entry point does with its batch once the bases lie in b->d_seq -- rc_correct_check
 // (a refused batch reaches no observer; an empty one is RC_OK with nothing staged), then on ctx's stream the observers' look at
 // the arena as it is, rc_correct_device_impl, and their look at it as corrected, staged into o.  stage_report: the report's
@@ -153,10 +153,12 @@ void rc_lane_error(rc_ctx *ctx, const rc_ctx *lane);
 // rc_api_table.hip
 // rc_recount_follow: the corrected arena in d_seq appended to the open session, on ctx's own stream; nothing without a session
 int rc_recount_take(rc_ctx *ctx, const void *d_seq, size_t nbytes);
-// rc_api_report.hip -- snapshot: the arena as it is, copied on ctx's stream; *snap = where (nullptr: none was taken).
+// rc_api_report.hip -- snapshot: the arena as it is, copied on ctx's stream, where the report is armed or a mate-overlap session
+// open and the batch has pairs (one copy for both; a single-end batch is copied for the report alone); *snap = where (nullptr:
+// none was taken).
 // count: the batch against that snapshot, straight into the report (stage == nullptr) or into stage->rep (zeroed first;
 // stage->rep_staged = something was launched).  commit: a staged block into the report.
-int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint8_t **snap);
+int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, bool pairs, const uint8_t **snap);
 int rc_report_count(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_split, uint32_t qual_base2, int qual_bits, const uint8_t *snap,
                     rc_batch_observed *stage);
 int rc_report_commit(rc_ctx *ctx, const rc_dbuf *staged);
@@ -169,4 +171,9 @@ int rc_dups_commit(rc_ctx *ctx, rc_batch_observed *o);
 // into the second, on ctx's stream.  commit: the pair added to the profile, complete on return.
 int rc_trust_stage(rc_ctx *ctx, const rc_device_batch *b, int version, rc_trust_staged *st);
 int rc_trust_commit(rc_ctx *ctx, rc_trust_staged *st);
+// rc_api_overlap.hip -- stage: behind the last correction kernel, st's rc_mate_overlap zeroed and the batch's pairs counted
+// into it, snap (rc_report_snapshot's) against the arena as corrected, on ctx's stream; a single-end batch stages nothing.
+// commit: added to the session, complete on return.
+int rc_overlap_stage(rc_ctx *ctx, const rc_device_batch *b, const uint8_t *snap, rc_overlap_staged *st);
+int rc_overlap_commit(rc_ctx *ctx, rc_overlap_staged *st);
 }

@@ -207,6 +207,46 @@ bool write_trust_profile(const char *path, const rc_trust_profile &T, bool two_m
     return fclose(fp) == 0 && ok;
 }
 
+void add_mate_overlap(rc_mate_overlap &to, const rc_mate_overlap &from)
+{
+    static_assert(sizeof(rc_mate_overlap) % 8 == 0, "64-bit counts throughout");
+    uint64_t *t = (uint64_t *)&to.pairs;
+    const uint64_t *f = (const uint64_t *)&from.pairs;
+    for (size_t i = 0; i < (sizeof(rc_mate_overlap) - offsetof(rc_mate_overlap, pairs)) / 8; ++i) t[i] += f[i];
+}
+
+std::string mate_overlap_text(const rc_mate_overlap &M)
+{
+    typedef unsigned long long ull;
+    std::string out;
+    char ln[256];
+    auto put = [&](const char *fmt, auto... a) {
+        snprintf(ln, sizeof ln, fmt, a...);
+        out += ln;
+    };
+    put("min_overlap\t%llu\nmax_mismatch_pct\t%llu\npairs\t%llu\noverlapping\t%llu\n", (ull)M.min_overlap, (ull)M.max_mismatch_pct, (ull)M.pairs, (ull)M.overlapping);
+    put("compared\tbefore\t%llu\ncompared\tafter\t%llu\n", (ull)M.compared_before, (ull)M.compared_after);
+    put("disagree\tbefore\t%llu\ndisagree\tafter\t%llu\n", (ull)M.disagree_before, (ull)M.disagree_after);
+    put("resolved\t%llu\nkept\t%llu\nintroduced\t%llu\n", (ull)M.resolved, (ull)M.kept, (ull)M.introduced);
+    put("pairs\timproved\t%llu\npairs\tworsened\t%llu\npairs\tsame\t%llu\n", (ull)M.pairs_improved, (ull)M.pairs_worsened, (ull)M.pairs_same);
+    for (int f = 0; f < RC_OVERLAP_FRAG_LEN; ++f)
+        if (M.frag[f]) put("frag\t%d\t%llu\n", f, (ull)M.frag[f]);
+    for (int m = 0; m < 2; ++m)
+        for (int p = 0; p < RC_OVERLAP_MAX_LEN; ++p)
+            if (M.compared5[m][p])
+                put("pos5\t%d\t%d\t%llu\t%llu\t%llu\n", m + 1, p, (ull)M.compared5[m][p], (ull)M.disagree5_before[m][p], (ull)M.disagree5_after[m][p]);
+    return out;
+}
+
+bool write_mate_overlap(const char *path, const rc_mate_overlap &M)
+{
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return false;
+    const std::string text = mate_overlap_text(M);
+    const bool ok = fwrite(text.data(), 1, text.size(), fp) == text.size();
+    return fclose(fp) == 0 && ok;
+}
+
 bool write_change_report(const char *path, const rc_change_report &R, bool two_mates)
 {
     FILE *fp = fopen(path, "wb");

@@ -185,6 +185,14 @@ bool write_dup_census(const char *path, const rc_dup_census &D, uint32_t max_bin
 // add_trust_profile: to += from, every count (what several GPUs' profiles become one with)
 bool write_trust_profile(const char *path, const rc_trust_profile &T, bool two_mates);
 void add_trust_profile(rc_trust_profile &to, const rc_trust_profile &from);
+// the mate-overlap report (rcorrector_amd.h: rc_mate_overlap) as tab-separated text: min_overlap <n> / max_mismatch_pct <n> /
+// pairs <n> / overlapping <n> / compared <before|after> <n> / disagree <before|after> <n> / resolved <n> / kept <n> / introduced
+// <n> / pairs <improved|worsened|same> <n> / frag <F> <pairs>, a line per non-zero F / pos5 <mate 1|2> <p> <compared> <disagree
+// before> <disagree after>, a line per position p (from 0, from that mate's 5' end) with compared > 0.
+// add_mate_overlap: to += from, every count (what several GPUs' reports become one with; the two parameters stay to's)
+std::string mate_overlap_text(const rc_mate_overlap &M);
+bool write_mate_overlap(const char *path, const rc_mate_overlap &M);
+void add_mate_overlap(rc_mate_overlap &to, const rc_mate_overlap &from);
 // GetBadQuality's two histograms over the records of one block (main.cpp:88-128), at most `room` of them
 void quality_histograms(const Block &b, int lpr, size_t room, std::vector<int32_t> &fh, std::vector<int32_t> &lh, int *total);
 

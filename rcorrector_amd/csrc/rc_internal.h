@@ -81,16 +81,25 @@ struct rc_trust_staged {
     int32_t min_count = 1;
 };
 
+// mate-overlap report: the counts of one batch in flight, an rc_mate_overlap in HBM, until the batch completes (staged == false:
+// none were taken); gen: the session they were taken for
+struct rc_overlap_staged {
+    rc_dbuf buf;
+    bool staged = false;
+    uint64_t gen = 0;
+};
+
 // What the batch observers (rc_api_observe.hip) keep for one batch in flight, from the submit that staged it to the completion
 // that accepts it: the duplicate census's keys (dup_units before | dup_units after; 0: none were taken) and the census they
-// were taken for, the trust profile's counts, and the correction report's counts where they are staged (rep_staged: this batch
-// left some).  One per slot, and one per context for the entry points that have no slot.
-enum { RC_OBS_DUPS = 1, RC_OBS_TRUST = 2, RC_OBS_REPORT = 4, RC_OBS_ALL = 7 };
+// were taken for, the trust profile's counts, the mate-overlap report's counts, and the correction report's counts where they
+// are staged (rep_staged: this batch left some).  One per slot, and one per context for the entry points that have no slot.
+enum { RC_OBS_DUPS = 1, RC_OBS_TRUST = 2, RC_OBS_REPORT = 4, RC_OBS_OVERLAP = 8, RC_OBS_ALL = 15 };
 struct rc_batch_observed {
     rc_dbuf dup_keys;
     size_t dup_units = 0;
     uint64_t dup_gen = 0;
     rc_trust_staged trust;
+    rc_overlap_staged ovl;
     rc_dbuf rep;
     bool rep_staged = false;
     // nothing staged any more for these observers; free_bufs: their buffers go too
@@ -213,6 +222,13 @@ struct rc_ctx {
     int32_t trust_min = 1;
     uint64_t trust_gen = 0;
     rc_dbuf trust_planes, trust_part;
+    // mate-overlap report (rc_mate_overlap_begin; kernel in rc_overlap.hip).  In the context it was opened on (the batches of its
+    // slot lanes add to it too: rc_home): ovl_acc, an rc_mate_overlap in HBM, the two thresholds, and ovl_gen, which counts the
+    // begins; the lanes' waits add under obs_mutex.  The arena as it arrived is rep_snap, the correction report's copy
+    std::atomic<bool> ovl_open{false};  // (read by the lanes' submits without the mutex)
+    void *ovl_acc = nullptr;
+    int32_t ovl_min = 30, ovl_pct = 10;
+    uint64_t ovl_gen = 0;
     // in the context a batch RUNS in: what the observers staged for the batch of an entry point that has no slot
     // (rc_correct_device, rc_correct_batch_traced)
     rc_batch_observed obs;
@@ -379,6 +395,11 @@ int rc_launch_weak_planes(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, int 
 int rc_launch_trust_profile(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int max_read_len, int mode,
                             int min_count, rc_dbuf *planes, rc_dbuf *partials, void *d_counts);
 int rc_launch_trust_add(rc_ctx *ctx, const void *d_src, void *d_dst, uint32_t n_words);
+
+// rc_overlap.hip: the pairs of two arenas that share d_off (mode 1 or 2, n_reads / 2 pairs), added to d_counts (an rc_mate_overlap
+// in HBM); max_read_len picks the instance
+int rc_launch_mate_overlap(rc_ctx *ctx, const uint8_t *d_before, const uint8_t *d_after, size_t nbytes, const uint32_t *d_off, uint32_t n_reads,
+                           int max_read_len, int mode, int min_overlap, int max_mismatch_pct, void *d_counts);
 
 // rc_dups.hip: one 128-bit key per unit of an arena (mode as rc_device_batch: n_reads units, or n_reads / 2 pairs) on stream st;
 // the census of n keys in HBM (left as they are) into host arrays copies[max_bin + 1], *distinct -- synchronous

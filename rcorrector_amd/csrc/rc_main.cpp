@@ -32,6 +32,9 @@
 // -trust-by-pos FILE writes the k-mer trust profile by read position (rcorrector_amd.h: rc_trust_profile; rc_format.h:
 // write_trust_profile): the reads with a solid / weak k-mer window at every position from either end, per mate, as uploaded and
 // as corrected, counted on the GPU as the batches complete (-weak-min: the count below which a k-mer is weak).
+// -overlap FILE writes the mate-overlap report (rcorrector_amd.h: rc_mate_overlap; rc_format.h: write_mate_overlap): where mate 1
+// and the reverse complement of mate 2 cover the same bases, the bases they disagree on before and after correction -- resolved,
+// kept, introduced -- and the fragment lengths (-overlap-min / -overlap-mm: the shortest overlap and the most mismatches accepted).
 #include <fcntl.h>
 #include <malloc.h>
 #include <sys/stat.h>
@@ -92,6 +95,13 @@ static void print_help()
             "\t\tcorrection: the reads that have a window there and those whose window is solid (in the table at least -weak-min\n"
             "\t\ttimes), weak, or invalid (holds a letter outside ACGT); one more line on stderr gives the weak share of the valid\n"
             "\t\twindows before and after; with -gpus above 1 the GPUs' counts are added up; not with -verbose\n"
+            "\t-overlap STRING: also write the mate-overlap report, tab-separated text (paired input only, -p / -i): where mate 1 and the\n"
+            "\t\treverse complement of mate 2 overlap, the bases the two disagree on before and after correction -- resolved, kept and\n"
+            "\t\tintroduced (probable miscorrections) -- by position from each mate's 5' end, and the fragment lengths; the offset of a\n"
+            "\t\tpair is chosen on the bases as read; one more line on stderr gives the disagreement rate before and after; with -gpus\n"
+            "\t\tabove 1 the GPUs' counts are added up; not with -r files, not with -verbose\n"
+            "\t-overlap-min INT: with -overlap, the fewest positions with two valid bases an overlap must have, 1-1023 (default: 30)\n"
+            "\t-overlap-mm INT: with -overlap, the most mismatches accepted, in percent of those positions, 0-50 (default: 10)\n"
             "\t-verbose-iter INT: threshold iterations recorded per read for -verbose (default: 64)\n");
 }
 
@@ -105,6 +115,8 @@ int main(int argc, char **argv)
     int max_fix_per_k = 4, i;
     double wk = 0.95;
     const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr, *report = nullptr, *dups = nullptr, *trust = nullptr;
+    const char *overlap = nullptr;
+    int overlap_min = 30, overlap_mm = 10;
     long dups_max = 10000;
     long histo_max = 10000;
     std::string od = "./";
@@ -169,6 +181,12 @@ int main(int argc, char **argv)
             dups_max = atol(argv[++i]);
         else if (!strcmp("-trust-by-pos", argv[i]))
             trust = argv[++i];
+        else if (!strcmp("-overlap", argv[i]))
+            overlap = argv[++i];
+        else if (!strcmp("-overlap-min", argv[i]))
+            overlap_min = atoi(argv[++i]);
+        else if (!strcmp("-overlap-mm", argv[i]))
+            overlap_mm = atoi(argv[++i]);
         else if (!strcmp("-weak-ends", argv[i]))
             run.weak_ends = true;
         else if (!strcmp("-weak-min", argv[i]))
@@ -187,6 +205,9 @@ int main(int argc, char **argv)
     if (run.weak_ends && verbose) die("rcorrector: usage: -weak-ends cannot be combined with -verbose (the transcript's entry point takes no weak-k-mer profile)\n");
     if (dups && verbose) die("rcorrector: usage: -dups cannot be combined with -verbose (small batches through the transcript's entry point: run the census without it)\n");
     if (trust && verbose) die("rcorrector: usage: -trust-by-pos cannot be combined with -verbose (small batches through the transcript's entry point: run the profile without it)\n");
+    if (overlap && verbose) die("rcorrector: usage: -overlap cannot be combined with -verbose (small batches through the transcript's entry point: run the report without it)\n");
+    if (overlap && (overlap_min < 1 || overlap_min > 1023)) die("rcorrector: usage: -overlap-min must be 1..1023\n");
+    if (overlap && (overlap_mm < 0 || overlap_mm > 50)) die("rcorrector: usage: -overlap-mm must be 0..50\n");
     if (dups && (dups_max < 1 || dups_max > (1l << 28))) die("rcorrector: usage: -dups-max must be 1..%ld\n", 1l << 28);
     if (run.weak_min < 1) die("rcorrector: usage: -weak-min must be at least 1\n");
     if (g_trace_iter < 1) g_trace_iter = 1;
@@ -543,6 +564,15 @@ int main(int argc, char **argv)
         for (int c = 0; c < nctx; ++c)
             if (rc_trust_profile_begin(ctx[c], run.weak_min)) die("rcorrector: %s\n", rc_last_error(ctx[c]));
 
+    // -overlap: every context counts the batches of pairs that complete on it, whatever the transport
+    if (overlap) {
+        for (const ReadFile &f : files)
+            if (!f.paired && !f.interleaved)
+                die("rcorrector: usage: -overlap compares the two mates of a pair: give paired files (-p / -i), no single-end ones (-r)\n");
+        for (int c = 0; c < nctx; ++c)
+            if (rc_mate_overlap_begin(ctx[c], overlap_min, overlap_mm)) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+    }
+
     // pipeline: reader (this thread) -> `inflight` workers per GPU -> writer thread (input order)
     warm.join();
     stamp("batch buffers ready");
@@ -632,6 +662,21 @@ int main(int argc, char **argv)
         fprintf(stderr, "Trust by position (k-mers counted below %d are weak): %llu of %llu valid k-mer windows weak before correction (%.4f), %llu of %llu after (%.4f)\n",
                 run.weak_min, (unsigned long long)weak[0], (unsigned long long)valid[0], valid[0] ? (double)weak[0] / (double)valid[0] : 0.0,
                 (unsigned long long)weak[1], (unsigned long long)valid[1], valid[1] ? (double)weak[1] / (double)valid[1] : 0.0);
+    }
+    if (overlap) {  // the contexts' counts, added up
+        std::vector<rc_mate_overlap> mo(2);
+        for (int c = 0; c < nctx; ++c) {
+            if (rc_mate_overlap_get(ctx[c], &mo[c ? 1 : 0])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+            if (c) add_mate_overlap(mo[0], mo[1]);
+            if (rc_mate_overlap_end(ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+        }
+        if (!write_mate_overlap(overlap, mo[0])) die("rcorrector: could not write %s\n", overlap);
+        const rc_mate_overlap &M = mo[0];
+        fprintf(stderr, "Mate overlap (at least %d bases, at most %d %% mismatches): %llu of %llu pairs overlap; %llu of %llu compared bases disagree before correction (%.6f), %llu of %llu after (%.6f); %llu introduced\n",
+                overlap_min, overlap_mm, (unsigned long long)M.overlapping, (unsigned long long)M.pairs, (unsigned long long)M.disagree_before,
+                (unsigned long long)M.compared_before, M.compared_before ? (double)M.disagree_before / (double)M.compared_before : 0.0,
+                (unsigned long long)M.disagree_after, (unsigned long long)M.compared_after,
+                M.compared_after ? (double)M.disagree_after / (double)M.compared_after : 0.0, (unsigned long long)M.introduced);
     }
     if (histo_after) {
         const double th0 = now_s();
