@@ -132,8 +132,298 @@ def polya_boundary_reads(k, seed=4242, n_tx=6, l_tx=400, cover=40, length=100):
     return np.stack(reads), np.stack(quals)
 
 
+# ---- qv_*: reads on which the base qualities decide what the three closing vetoes of the correction do ----
+# (pairwise veto, end-of-read veto, density veto: ErrorCorrection.cpp:1314-1466).  The sets above give every substituted base a
+# quality below the threshold and every other base one above it, so no veto ever sees a fix on a high-quality base.  Here clean
+# reads get bursts of substitutions shaped for one veto each, and the qualities come from a model of their own.
+
+# the lengths of qv_lengths: either side of the 64-bit words of the veto masks, of the `len > 10` test, of end windows that
+# overlap, and of the S / M / L tiers
+QV_LENGTHS = [11, 12, 19, 20, 21, 63, 64, 65, 127, 128, 129, 160, 161, 191, 192, 193, 255, 256, 257, 278, 279, 320, 1023]
+QV_MODELS = ("high", "inverted", "straddle", "fasta", "low", "signed")
+_QV_SEED = {"pair": 8100, "ends": 8200, "dense": 8300, "mixed": 8400, "lengths": 8500, "signed": 8600}
+
+
+def _substitute(rng, s, err, i, pos):
+    for p in pos:
+        s[i, p] = synth.NUC[(synth.CODE[s[i, p]] + int(rng.integers(1, 4))) & 3]
+        err[i, p] = True
+
+
+def _burst(rng, family, length, k, mfk):
+    """The positions one read's substitutions go to (empty: the read stays clean)."""
+    if family == "ends":
+        # 2..4 in the first ten and / or the last ten bases, and singles in between (at least 12 bases apart) up to 4..6 in all
+        if rng.random() >= 0.7:
+            return []
+        which = int(rng.integers(0, 3))
+        pos = []
+        if which != 1:
+            pos += list(rng.choice(10, int(rng.integers(2, 5)), replace=False))
+        if which != 0:
+            pos += list(length - 10 + rng.choice(10, int(rng.integers(2, 5)), replace=False))
+        want = max(4, len(pos)) + int(rng.integers(0, 3)) - len(pos)
+        slots = rng.permutation(np.arange(16, length - 16, 12))[:want]
+        return pos + [int(x) + int(rng.integers(0, 4)) for x in slots]
+    if family == "dense":
+        # mfk..mfk+3 inside one k-window, anywhere in the read (mfk = 1: 1..3, and 2 in three cases of five: with one fix per
+        # window allowed, it is the window with two on which the weights decide)
+        if rng.random() >= 0.7:
+            return []
+        m = int(rng.choice([1, 2, 2, 2, 3])) if mfk == 1 else int(rng.integers(mfk, mfk + 4))
+        span = int(rng.integers(m, k + 1))
+        a = int(rng.integers(0, length - span + 1))
+        return list(a + rng.choice(span, m, replace=False))
+    if family in ("mixed", "signed"):
+        # 2..5 inside a span of 3..k+3 bases: 30 % at the 5' end, 30 % at the 3' end, the rest anywhere
+        if rng.random() >= 0.6:
+            return []
+        m, where, span = int(rng.integers(2, 6)), rng.random(), int(rng.integers(3, k + 4))
+        a = 0 if where < 0.3 else (length - span if where < 0.6 else int(rng.integers(0, length - span)))
+        return list(a + rng.choice(span, min(m, span), replace=False))
+    if family == "pair":
+        return []   # (exactly the two substitutions of a minor haplotype: qv_reads)
+    if family == "lengths":
+        # 2..4 at each end (drawn separately, so end windows that overlap may share bases), and one more in the middle
+        if length < 11 or rng.random() >= 0.9:
+            return []
+        pos = set(rng.choice(10, int(rng.integers(2, 5)), replace=False).tolist())
+        pos |= set((length - 10 + rng.choice(10, int(rng.integers(2, 5)), replace=False)).tolist())
+        if length > 40 and rng.random() < 0.5:
+            pos.add(int(rng.integers(15, length - 15)))
+        return sorted(pos)
+    raise KeyError(family)
+
+
+_QV_READS = {}
+# per family: reads (mode 0) or pairs, transcripts, transcript length, share of the reads that carry a minor haplotype
+_QV_SHAPE = {"pair": (1500, 8, 500, 0.2), "ends": (1500, 8, 500, 0.0), "dense": (1500, 8, 500, 0.0), "mixed": (1500, 8, 500, 0.06),
+             "lengths": (600, 3, 1500, 0.2), "signed": (1000, 8, 500, 0.06)}
+
+
+def qv_reads(family, k, mfk, mode, shape=None):
+    """(seq arrays, error masks, lengths, keys, counts) of one qv_ family, with the exact counts of the reads' own k-mers as the
+    table.  The reads are windows of a few deeply covered transcripts, either strand; the two mates of a pair are the two ends of
+    a 300-base fragment and get their substitutions independently.  Two kinds of substitution:
+      * a minor haplotype: every transcript has pairs of sites 2..k bases apart (an eighth of them k - 1 apart, the last distance
+        at which one k-mer covers both, an eighth k apart, the first at which none does), a pair every 7 bases; a read
+        that holds a pair at least 12 bases from either end carries, with the family's probability, other bases at both
+        sites -- and its unit is then sequenced two or three times, as duplicates of a fragment are: same windows, same
+        haplotypes.  So the minor k-mers have counts of 2 or 3, few enough to be distrusted and alike enough for the pairwise
+        veto, which weighs the k-mers over one fix against those over both, to fire.  Substitutions drawn per read give
+        k-mers nobody else has, and the veto never fires on them.
+      * the family's burst (_burst), different in every read, duplicates included.
+    shape: (units, transcripts, transcript length, share of minor haplotypes) in place of the family's own (_QV_SHAPE).
+    Built once per argument tuple; nothing changes the arrays."""
+    key = (family, k, mfk, mode, shape)
+    if key in _QV_READS:
+        return _QV_READS[key]
+    rng = np.random.Generator(np.random.PCG64(_QV_SEED[family] + 37 * k + mfk + 1000 * mode))
+    n, n_tx, l_tx, p_var = shape or _QV_SHAPE[family]
+    if mfk == 1:
+        n = 2000
+    paired, frag = mode != 0, 300
+    if paired:
+        n //= 2
+    mates = 2 if paired else 1
+    tx = rng.integers(0, 4, size=(n_tx, l_tx), dtype=np.uint8)
+    sites = [[] for _ in range(n_tx)]   # per transcript: (first site, second site)
+    for t in range(n_tx):
+        for a in range(8, l_tx - k - 1, 7):
+            u = rng.random()
+            dist = k - 1 if u < 0.125 else k if u < 0.25 else int(rng.integers(2, k + 1))
+            sites[t].append((a, a + dist))
+    # 1. the units: per mate (transcript, window start, reverse strand?, length, minor haplotype or None), each unit once, or
+    #    two or three times where a mate carries a minor haplotype
+    units = []
+    while len(units) < n:
+        t, rev = int(rng.integers(0, n_tx)), bool(rng.integers(0, 2))
+        ulens = [int(rng.choice(QV_LENGTHS)) if family == "lengths" else 100 for _ in range(mates)]
+        span = frag if paired else ulens[0]
+        start = int(rng.integers(0, l_tx - span + 1))
+        unit = []
+        for j, ln in enumerate(ulens):
+            rc = rev != (j == 1)
+            ws = start + span - ln if rc and paired else start
+            inner = [(a, b) for a, b in sites[t] if a - ws >= 12 and b - ws < ln - 12]
+            minor = None
+            if inner and rng.random() < p_var:
+                a, b = inner[int(rng.integers(0, len(inner)))]
+                minor = (a - ws, b - ws, (tx[t, a] + rng.integers(1, 4)) & 3, (tx[t, b] + rng.integers(1, 4)) & 3)
+            unit.append((t, ws, rc, ln, minor))
+        times = 1 + int(rng.integers(1, 3)) if any(m[4] is not None for m in unit) else 1
+        units += [unit] * times
+    units = units[:n]
+    # 2. the reads of every unit, each with a burst of its own
+    length = max(QV_LENGTHS) if family == "lengths" else 100
+    lens = [np.array([u[j][3] for u in units]) for j in range(mates)]
+    seqs = [np.full((n, length), ord("N"), np.uint8) for _ in range(mates)]
+    errs = [np.zeros((n, length), bool) for _ in range(mates)]
+    for i, unit in enumerate(units):
+        for j, (t, ws, rc, ln, minor) in enumerate(unit):
+            r = tx[t, ws:ws + ln].copy()
+            e = np.zeros(ln, bool)
+            if minor is not None:
+                r[minor[0]], r[minor[1]] = minor[2], minor[3]
+                e[minor[0]] = e[minor[1]] = True
+            if rc:
+                r, e = (3 - r)[::-1], e[::-1]
+            seqs[j][i, :ln], errs[j][i, :ln] = synth.NUC[r], e
+            _substitute(rng, seqs[j], errs[j], i, _burst(rng, family, ln, k, mfk))
+    keys, cnt = synth.count_kmers(seqs, k, lens)
+    for a in seqs + errs + lens + [keys, cnt]:
+        a.setflags(write=False)
+    _QV_READS[key] = (seqs, errs, lens, keys, cnt)
+    return _QV_READS[key]
+
+
+def qv_quals(model, err, thr, seed):
+    """The quality bytes of one arena of reads.  high: all thr + 1.  inverted: thr + 1 on the substituted bases, thr on the
+    others (the opposite of what the older sets do).  straddle: uniform in thr - 2 .. thr + 2, so a fifth of the bytes equal the
+    threshold (capped at 127: as a signed char, what the comparison works on, 128 is the lowest value there is).  low: all equal
+    to the threshold -- the control, on which no quality test is ever true.  fasta: none (qual[0] == 0).  signed: half the
+    bytes are thr + 1 or thr + 2, the other half are uniform in 0x80 .. 0xFF, which are negative as signed chars and so below any threshold."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    if model == "high":
+        return np.full(err.shape, thr + 1, np.uint8)
+    if model == "inverted":
+        return np.where(err, thr + 1, thr).astype(np.uint8)
+    if model == "straddle":
+        return rng.integers(thr - 2, min(127, thr + 2) + 1, err.shape).astype(np.uint8)
+    if model == "low":
+        return np.full(err.shape, thr, np.uint8)
+    if model == "fasta":
+        return np.zeros(err.shape, np.uint8)
+    if model == "signed":
+        q = rng.integers(thr + 1, thr + 3, err.shape)
+        return np.where(rng.random(err.shape) < 0.5, rng.integers(0x80, 0x100, err.shape), q).astype(np.uint8)
+    raise KeyError(model)
+
+
+def qv_name(family, model, k=23, mfk=None, thr="H"):
+    """qv_<family>[_k<k>][_mfk<m>][_q<threshold byte>]/<quality model>"""
+    return "qv_%s%s%s%s/%s" % (family, "" if k == 23 else "_k%d" % k, "" if mfk is None else "_mfk%d" % mfk,
+                               "" if thr == "H" else "_q%d" % ord(thr), model)
+
+
+def _qv_names():
+    """Each family with the quality models that make sense for it:
+      * fasta only where minor haplotypes give the pairwise veto something to weigh (pair, mixed, lengths).  Without qualities the
+        other two vetoes see no high-quality base at all, so the pairwise veto is the only one a missing quality array changes:
+        on qv_ends and qv_dense, whose substitutions are drawn per read, it never fires, and a fasta member measured 0 to 3
+        quality-dependent reads -- no such member can meet the floor of 30.
+      * inverted only at k = 23, threshold 'H': it differs from high on the bases that are not substituted, which the vetoes
+        look at only where the search proposes a wrong fix; one member per family pins that, qv_lengths (600 reads) has none.
+      * qv_dense at max_fix_per_k 1, 3, 4, 5: high (every weight 2) and straddle (weights mixed, bytes on the threshold); the
+        full set of models is on the max_fix_per_k = 2 member, the one that the alternative kernel paths run as well.
+      * the other k and thresholds: high and straddle (qv_mixed_pe at other k: straddle), the two that differ most."""
+    names = [qv_name(f, m) for f in ("pair", "mixed_pe", "mixed_il") for m in ("high", "inverted", "straddle", "fasta", "low")]
+    names += [qv_name("ends", m) for m in ("high", "inverted", "straddle", "low")]
+    names += [qv_name("dense", m, mfk=2) for m in ("high", "inverted", "straddle", "low")]
+    names += [qv_name("dense", m, mfk=mfk) for mfk in (1, 3, 4, 5) for m in ("high", "straddle")]
+    names += [qv_name("lengths", m) for m in ("high", "straddle", "fasta", "low")]
+    for k in (11, 15, 25, 31, 32):
+        names += [qv_name("pair", "high", k=k), qv_name("pair", "straddle", k=k), qv_name("mixed_pe", "straddle", k=k)]
+    names += [qv_name("mixed_pe", m, thr=t) for t in "!~" for m in ("high", "straddle")]
+    return names + ["qv_signed/signed"]
+
+
+QV_NAMES = _qv_names()
+# the high and inverted members of qv_pair, qv_ends, qv_dense and qv_mixed_*, at every k and threshold: at least 100 reads
+# each on which the qualities decide (quality_dependent); at least 30 on every other set but the controls
+QV_STRONG = [n for n in QV_NAMES if n.split("/")[1] in ("high", "inverted") and n.split("_")[1].split("/")[0] in ("pair", "ends", "dense", "mixed")]
+
+
+def qv_make(name, shape=None):
+    """shape: see qv_reads (a smaller instance of the same recipe, for a fixture)"""
+    base, model = name.split("/")
+    parts = base.split("_")[1:]
+    opts = {p[0] if p[0] in "kq" else "mfk": int(p.lstrip("kmfq")) for p in parts if p[-1].isdigit()}
+    family = [p for p in parts if not p[-1].isdigit()]
+    mode = {"pe": 1, "il": 2}.get(family[-1], 0)
+    family = family[0]
+    k, thr = opts.get("k", 23), opts.get("q", ord("H"))
+    mfk = opts.get("mfk", {"pair": 4, "ends": 8, "mixed": 4, "lengths": 4, "signed": 4}.get(family))
+    seqs, errs, lens, keys, cnt = qv_reads(family, k, mfk if family == "dense" else 0, mode, shape)
+    seed = _QV_SEED[family] + 37 * k + 7
+    rows = [[s[i, :ln[i]].tobytes() for i in range(len(s))] for s, ln in zip(seqs, lens)]
+    quals = [[q[i, :ln[i]].tobytes() for i in range(len(q))] for q, ln in
+             zip([qv_quals(model, e, thr, seed + j) for j, e in enumerate(errs)], lens)]
+    r1, q1, r2, q2 = rows[0], quals[0], None, None
+    if mode == 1:
+        r2, q2 = rows[1], quals[1]
+    elif mode == 2:
+        r1 = [x for p in zip(*rows) for x in p]
+        q1 = [x for p in zip(*quals) for x in p]
+    return dict(k=k, mfk=mfk, rate=0.01, mode=mode, keys=keys, counts=cnt, seqs1=r1, quals1=q1, seqs2=r2, quals2=q2,
+                badq=bytes([thr]), fasta=model == "fasta", control=model == "low")
+
+
+def with_quals(d, byte):
+    """d with every quality byte set to `byte`"""
+    flat = lambda rows: None if rows is None else [bytes([byte]) * len(r) for r in rows]
+    return dict(d, quals1=flat(d["seqs1"]), quals2=flat(d["seqs2"]))
+
+
+def quality_dependent(oracle, d, want=None):
+    """The number of reads whose (ret, corrected bases) differ between d and the same reads with every quality byte set to the
+    threshold -- that is, with no quality test of any veto ever true.  `want`: the oracle's results on d, where the caller has them."""
+    want = run_oracle(oracle, d) if want is None else want
+    flat = run_oracle(oracle, with_quals(d, d.get("badq", b"H")[0]))
+    n_units = len(d["seqs1"])
+    differ = want[0] != flat[0]
+    for j, (a, b) in enumerate(zip(want[4:], flat[4:])):
+        off = oracle.pack_reads(d["seqs1"] if j == 0 else d["seqs2"])[1].astype(np.int64)
+        rows = np.add.reduceat((a != b).astype(np.int64), off[:-1]) > 0
+        differ[j * n_units:(j + 1) * n_units] |= rows
+    return int(differ.sum())
+
+
+def for_cli(d, seed=8800):
+    """d with the first and the last quality byte of every read redrawn so that the command-line tools, which derive the
+    threshold from exactly these bytes (main.cpp:88-128: the lower of the 5 % point of the first bytes, less one, and the 5 %
+    point of the last bytes), arrive at the data set's own threshold: first bytes thr + 4, last bytes uniform in thr .. thr + 2.
+    Left alone, a set whose bytes all lie within two of the threshold gets a threshold below every one of them."""
+    if d.get("fasta", False):
+        return d
+    rng = np.random.Generator(np.random.PCG64(seed))
+    thr = d["badq"][0]
+    redraw = lambda quals: None if quals is None else [bytes([thr + 4]) + q[1:-1] + bytes([thr + int(rng.integers(0, 3))]) for q in quals]
+    return dict(d, quals1=redraw(d["quals1"]), quals2=redraw(d["quals2"]))
+
+
+def write_cli_case(d, path, units=None):
+    """Data set d (its first `units` reads or pairs) as input files of the command-line tools in directory `path`: dump.jf and
+    reads.fq / reads_1.fq + reads_2.fq / reads_il.fq (reads.fa for a set without qualities).  Returns the arguments, -maxcorK as
+    the data set says; the tools derive the quality threshold from the reads themselves."""
+    import os
+    synth.write_dump(os.path.join(path, "dump.jf"), d["keys"], d["counts"], d["k"])
+    fasta = d.get("fasta", False)
+
+    def put(name, seqs, quals, tag=lambda i: b""):
+        with open(os.path.join(path, name), "wb") as f:
+            for i, (s, q) in enumerate(zip(seqs, quals)):
+                f.write(b">r%d%s\n%s\n" % (i, tag(i), s) if fasta else b"@r%d%s\n%s\n+\n%s\n" % (i, tag(i), s, q))
+    ext = "fa" if fasta else "fq"
+    if d["mode"] == 1:
+        put("reads_1." + ext, d["seqs1"][:units], d["quals1"][:units], lambda i: b"/1")
+        put("reads_2." + ext, d["seqs2"][:units], d["quals2"][:units], lambda i: b"/2")
+        args = ["-p", "reads_1." + ext, "reads_2." + ext]
+    elif d["mode"] == 2:
+        n = None if units is None else 2 * units
+        put("reads_il." + ext, d["seqs1"][:n], d["quals1"][:n], lambda i: b"/%d" % (i % 2 + 1))
+        args = ["-i", "reads_il." + ext]
+    else:
+        put("reads." + ext, d["seqs1"][:units], d["quals1"][:units])
+        args = ["-r", "reads." + ext]
+    return args + ["-k", str(d["k"]), "-c", "dump.jf", "-maxcorK", str(d["mfk"])]
+
+
 def make(name):
-    """Returns dict(k, mfk, rate, mode, keys, counts, seqs1, quals1, seqs2, quals2) as python bytes lists."""
+    """Returns dict(k, mfk, rate, mode, keys, counts, seqs1, quals1, seqs2, quals2) as python bytes lists; the qv_ sets also carry
+    their threshold byte (badq)."""
+    if name.startswith("qv_"):
+        return qv_make(name)
     if name.startswith("polya_k"):
         k = int(name[len("polya_k"):])
         s1, q1 = polya_boundary_reads(k)
@@ -176,6 +466,21 @@ def revcomp_codes(codes, k):
     return out
 
 
+def pad_table(keys, cnt, k, pad_to, seed):
+    """(keys, counts) padded to pad_to entries with canonical k-mers that are not among `keys` (counts 2..199): a table of the
+    size -- and so the layout and the compiled-for-k kernel instance -- of a real one, which changes no read's k-mer counts."""
+    if pad_to <= len(keys):
+        return keys, cnt
+    rng = np.random.Generator(np.random.PCG64(seed))
+    mask = np.uint64((1 << (2 * k)) - 1) if k < 32 else np.uint64(0xFFFFFFFFFFFFFFFF)
+    fwd = rng.integers(0, 1 << 63, size=pad_to + pad_to // 8, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=pad_to + pad_to // 8, dtype=np.uint64)
+    fwd &= mask
+    pad = np.unique(np.minimum(fwd, revcomp_codes(fwd, k)))
+    pad = rng.permutation(pad[~np.isin(pad, keys)])[:pad_to - len(keys)]
+    assert len(keys) + len(pad) == pad_to, "k = %d has too few k-mers to pad a table to %d entries" % (k, pad_to)
+    return np.concatenate([keys, pad]), np.concatenate([cnt, rng.integers(2, 200, size=len(pad)).astype(np.int64)])
+
+
 def k_sweep(k, mode, pad_to=0):
     """The k sweep's data set (tests/test_k_sweep.py): 600 reads (mode 1: pairs) of 100 bases over six transcripts of 400,
     1 % substitutions, the exact counts of their own k-mers as the table.  With pad_to > 0 the table is padded to that many
@@ -183,16 +488,7 @@ def k_sweep(k, mode, pad_to=0):
     compiled-for-k kernel instance -- of a real one; the oracle gets the same padded table."""
     s1, q1, s2, q2, _ = synth.make_reads(7100 + k, 600, 100, n_tx=6, l_tx=400, e=0.01, paired=mode == 1)
     keys, cnt = synth.count_kmers([s1, s2], k)
-    if pad_to > len(keys):
-        rng = np.random.Generator(np.random.PCG64(9100 + k))
-        mask = np.uint64((1 << (2 * k)) - 1) if k < 32 else np.uint64(0xFFFFFFFFFFFFFFFF)
-        fwd = rng.integers(0, 1 << 63, size=pad_to + pad_to // 8, dtype=np.uint64) * np.uint64(2) + rng.integers(0, 2, size=pad_to + pad_to // 8, dtype=np.uint64)
-        fwd &= mask
-        pad = np.unique(np.minimum(fwd, revcomp_codes(fwd, k)))
-        pad = rng.permutation(pad[~np.isin(pad, keys)])[:pad_to - len(keys)]
-        assert len(keys) + len(pad) == pad_to, "k = %d has too few k-mers to pad a table to %d entries" % (k, pad_to)
-        keys = np.concatenate([keys, pad])
-        cnt = np.concatenate([cnt, rng.integers(2, 200, size=len(pad)).astype(np.int64)])
+    keys, cnt = pad_table(keys, cnt, k, pad_to, 9100 + k)
 
     def rows(a):
         return None if a is None else [r.tobytes() for r in a]
@@ -204,7 +500,7 @@ def run_oracle(po, d, threads=4, fn=None):
     Returns (ret, l, m, h, corrected_arena1[, corrected_arena2])."""
     T = po.Table(d["k"], len(d["keys"]))
     T.put_many(d["keys"], d["counts"])
-    P = po.make_params(d["k"], d["mfk"], d["rate"], b"H")
+    P = po.make_params(d["k"], d["mfk"], d["rate"], d.get("badq", b"H"))
     a, off = po.pack_reads(d["seqs1"])
     qa, _ = po.pack_reads(d["quals1"])
     if d["mode"] == 1:

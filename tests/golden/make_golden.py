@@ -125,6 +125,32 @@ def main():
     dump_of(os.path.join(d, "dump.jf"), [s1], 23)
     fq(os.path.join(d, "reads.fq"), r, q)
     run_ref(d, ["-r", "reads.fq", "-k", "23", "-c", "dump.jf"])
+    # --- qualities that decide (tests/datasets.py: the recipe of qv_mixed_pe/straddle at a size that keeps the fixture small,
+    # 150 pairs over two transcripts of 400 bases, the same 37-fold coverage, and their own k-mers as the table):
+    # bursts of substitutions at the ends and inside one k-window, minor haplotypes, and quality bytes within two of each
+    # other, with first and last bytes such that the threshold the reference derives from them (main.cpp:88-128) is the 'H' in
+    # their middle (datasets.for_cli).  What makes the fixture worth having is asserted: with every quality byte set to the
+    # lowest of them the reference writes at least 30 records differently.
+    d = os.path.join(HERE, "fx_qual_veto")
+    os.makedirs(d, exist_ok=True)
+    ds = datasets.for_cli(datasets.qv_make("qv_mixed_pe/straddle", shape=(300, 2, 400, 0.06)))
+    args = datasets.write_cli_case(ds, d, units=None)
+    run_ref(d, args)
+    assert b"Bad quality threshold is 'H'" in open(os.path.join(d, "ref", "stderr.txt"), "rb").read()
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        lowest = bytes([min(min(q) for q in ds["quals1"] + ds["quals2"])])
+        flat = dict(ds, quals1=[lowest * len(q) for q in ds["quals1"]], quals2=[lowest * len(q) for q in ds["quals2"]])
+        os.makedirs(os.path.join(tmp, "out"))
+        subprocess.run([REF] + datasets.write_cli_case(flat, tmp, units=None) + ["-od", os.path.join(tmp, "out")], cwd=tmp, stderr=subprocess.DEVNULL, check=True)
+        differ = 0
+        for f in ("reads_1.cor.fq", "reads_2.cor.fq"):
+            a = open(os.path.join(d, "ref", f), "rb").read().split(b"\n")
+            b = open(os.path.join(tmp, "out", f), "rb").read().split(b"\n")
+            assert len(a) == len(b) == 4 * 150 + 1
+            differ += sum(a[i:i + 2] != b[i:i + 2] for i in range(0, 4 * 150, 4))   # (header with l / m / h and verdict, bases)
+    print("fx_qual_veto: %d of 300 records depend on their qualities" % differ)
+    assert differ >= 30, differ
     # --- FASTA input (Reads.h:108-162).  The reference's -t 1 loop hands ErrorCorrection a NULL quality
     # pointer for FASTA records and crashes in the pairwise veto (main.cpp:376-379, ErrorCorrection.cpp:1316);
     # its batch path (-t > 1) passes a buffer whose first byte is 0 (Reads.h:241) and works: that is the

@@ -110,7 +110,7 @@ def expected(po, name, fasta=False):
         d = _dataset(name)
         T = po.Table(d["k"], len(d["keys"]))
         T.put_many(d["keys"], d["counts"])
-        P = po.make_params(d["k"], d["mfk"], d["rate"], BAD_Q)
+        P = po.make_params(d["k"], d["mfk"], d["rate"], d.get("badq", BAD_Q))
         ar = arenas_of(po, d, fasta)
         corr = [a.copy() for a, _, _ in ar]
         quals = [np.zeros_like(a) if q is None else q for a, q, _ in ar]   # (no qualities: the reference sees qual[0] == 0)
@@ -122,7 +122,7 @@ def expected(po, name, fasta=False):
         R = zero_report()
         for i, (a, q, off) in enumerate(ar):
             mate_of = (lambda r: r & 1) if d["mode"] == 2 else (lambda r, i=i: i)
-            R = add_reports(R, model(a, corr[i], off, ret[i * n:(i + 1) * n], q, mate_of))
+            R = add_reports(R, model(a, corr[i], off, ret[i * n:(i + 1) * n], q, mate_of, d.get("badq", BAD_Q)))
         assert consistent(R) > 0, "%s: the oracle changes nothing, the case would pass vacuously" % name
         _EXPECTED[key] = (R, int(ret[ret > 0].sum()))
     return _EXPECTED[key]
@@ -131,7 +131,7 @@ def expected(po, name, fasta=False):
 def new_ctx(d, qbits=False):
     ctx = rcorrector_amd.Context(k=d["k"], max_fix_per_k=d["mfk"], device=0)
     ctx.table_build(d["keys"], d["counts"])
-    ctx.set_run_params(d["rate"], BAD_Q)
+    ctx.set_run_params(d["rate"], d.get("badq", BAD_Q))
     if qbits:
         ctx.set_quality_bits(True)
     return ctx
@@ -155,7 +155,7 @@ def batch_of(po, ctx, d, lo, hi, qbits=False, fasta=False):
         a, off = po.pack_reads(s[lo:hi])
         qa = np.zeros_like(a) if fasta else po.pack_reads(q[lo:hi])[0]
         if qbits:
-            qa = ctx.pack_quality_bits(qa, BAD_Q)
+            qa = ctx.pack_quality_bits(qa, d.get("badq", BAD_Q))
         out += [a, qa, off]
     return out
 
@@ -222,7 +222,7 @@ def submit_packed(po, ctx, d, lo, hi, slot, fasta=False, fix_cap=None):
     qb = None
     if not fasta:
         qb = ctx.host_array((a.size + 7) // 8)
-        ctx.pack_quality_bits(qa, BAD_Q, out=qb)
+        ctx.pack_quality_bits(qa, d.get("badq", BAD_Q), out=qb)
     ctx.submit_packed(slot, d["mode"], a.size, off, bases, qb, exc_pos, exc_chr, fix_cap=fix_cap)
     return arena, bases, exc_pos, exc_chr, qb, off
 
@@ -247,7 +247,7 @@ def keep_arenas(po, ctx, d):
         ctx.count_add(a)
     ctx.count_finish(2)
     ctx.table_build(d["keys"], d["counts"])
-    ctx.set_run_params(d["rate"], BAD_Q)
+    ctx.set_run_params(d["rate"], d.get("badq", BAD_Q))
     return ar
 
 
@@ -266,7 +266,7 @@ def submit_resident(ctx, d, ar, lo, hi, slot, fasta=False, fix_cap=None):
     qb = None
     if not fasta:
         qb = ctx.host_array((b1 + args.get("bytes_b", 0) + 7) // 8)
-        ctx.pack_quality_bits(np.concatenate(qs), BAD_Q, out=qb)
+        ctx.pack_quality_bits(np.concatenate(qs), d.get("badq", BAD_Q), out=qb)
     ctx.submit_resident(slot, d["mode"], np.concatenate(off).astype(np.uint32), qb, fix_cap=fix_cap, **args)
     return qb
 
@@ -287,7 +287,7 @@ def via_device(po, ctx, d, nb, qbits=False, fasta=False):
     for lo, hi in unit_cuts(d, nb):
         a, qa, off, _ = one_arena(po, d, lo, hi, fasta)
         if qbits:
-            qa = ctx.pack_quality_bits(qa, BAD_Q)
+            qa = ctx.pack_quality_bits(qa, d.get("badq", BAD_Q))
         n = len(off) - 1
         t_buf = torch.zeros(a.size + 64, dtype=torch.uint8, device="cuda")
         t_seq = t_buf[5:5 + a.size]
@@ -313,7 +313,9 @@ TRANSPORTS = {"correct_batch": via_correct_batch, "slots": via_slots, "slots_lan
               "resident": via_resident, "device": via_device}
 # modes 0, 1 and 2; tiers_*: reads beyond 160 and 320 bases; edge: the adversarial reads (letters outside ACGT: the N row of
 # subst); pe_var / nrich: N-rich, variable lengths
-NAMES = ["se_k23", "pe_k23", "il_k23", "tiers_se", "tiers_pe", "tiers_il", "edge", "nrich", "pe_var"]
+# qv_mixed_pe/straddle: qualities either side of and on the threshold, fixes on both kinds of base (tests/datasets.py: qv_)
+QV = "qv_mixed_pe/straddle"
+NAMES = ["se_k23", "pe_k23", "il_k23", "tiers_se", "tiers_pe", "tiers_il", "edge", "nrich", "pe_var", QV]
 
 
 def run_case(oracle, name, tname, nb, qbits=False, fasta=False):
@@ -346,7 +348,9 @@ def test_report_equals_the_model_on_the_oracles_output(oracle, name, tname):
     if name.startswith("tiers"):
         assert int(want["len_hist"][:, 161:321].sum()) > 0 and int(want["len_hist"][:, 321:].sum()) > 0
         assert int(want["by_pos5"][:, 160:].sum()) > 0
-    if name in ("pe_k23", "il_k23", "tiers_pe", "tiers_il", "pe_var"):
+    if name == QV:
+        assert want["by_qual"][0] >= 50 and want["by_qual"][1] >= 50 and want["by_qual"][2] == 0
+    if name in ("pe_k23", "il_k23", "tiers_pe", "tiers_il", "pe_var", QV):
         assert want["reads"][0] == want["reads"][1] > 0 and want["changes"][1] > 0
     else:
         assert want["reads"][1] == 0 and int(want["by_pos5"][1].sum()) == 0
@@ -365,12 +369,14 @@ def test_report_of_reads_corrected_one_by_one(oracle, name):
 
 # ---- 2. the shapes quality arrives in ----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("tname", ["correct_batch", "slots", "device"])
-@pytest.mark.parametrize("name", ["se_k23", "pe_k23", "il_k23", "tiers_pe", "pe_var", "edge"])
+@pytest.mark.parametrize("name", ["se_k23", "pe_k23", "il_k23", "tiers_pe", "pe_var", "edge", QV])
 def test_quality_bits_give_the_same_report(oracle, name, tname):
     """rc_set_quality_bits: the byte entry points take bit arrays; a paired host batch has its second arena's bits apart
     (qual_split / qual_base2).  (tiers_pe: every change is on a low-quality base.)"""
     want = run_case(oracle, name, tname, 3, qbits=True)
     assert want["by_qual"][0] > 0 and (want["by_qual"][1] > 0 or name == "tiers_pe") and want["by_qual"][2] == 0
+    if name == QV:
+        assert want["by_qual"][0] >= 50 and want["by_qual"][1] >= 50
 
 
 @pytest.mark.parametrize("tname", ["correct_batch", "packed", "resident", "device", "correct_read"])
@@ -382,6 +388,13 @@ def test_a_batch_without_qualities_counts_as_none(oracle, tname):
 def test_a_paired_batch_without_qualities(oracle):
     run_case(oracle, "pe_k23", "packed", 2, fasta=True)
     run_case(oracle, "pe_k23", "slots", 2, fasta=True)
+
+
+@pytest.mark.parametrize("tname", ["correct_batch", "packed", "resident", "device"])
+def test_the_reads_on_which_qualities_decide_without_their_qualities(oracle, tname):
+    """qv_mixed_pe/fasta, the twin of QV: the same reads with no qualities, on which the pairwise veto is never skipped"""
+    want = run_case(oracle, QV, tname, 2, fasta=True)
+    assert want["by_qual"][2] == want["changes"].sum() >= 50 and want["by_qual"][0] == want["by_qual"][1] == 0
 
 
 # ---- 3. behaviour --------------------------------------------------------------------------------------------------------------------
@@ -463,7 +476,7 @@ def test_state_errors_and_an_empty_batch(oracle):
     assert L.rc_change_report_end(h) == RC_STATUS_STATE
     assert L.rc_change_report_get(h, C.byref(rep)) == RC_STATUS_STATE
     ctx.table_build(d["keys"], d["counts"])
-    ctx.set_run_params(d["rate"], BAD_Q)
+    ctx.set_run_params(d["rate"], d.get("badq", BAD_Q))
     ctx.change_report_begin()
     empty, off0 = np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.uint32)
     ctx.correct_batch(0, empty, empty, off0)

@@ -31,7 +31,7 @@ def test_cli_packed_transport_reproduces_reference_outputs(name, extra, tmp_path
 
 
 @pytest.mark.parametrize("lanes", ["1", "0"])
-@pytest.mark.parametrize("name", ["fx_se_k23", "fx_pe_k23", "fx_il_k23", "fx_edge"])
+@pytest.mark.parametrize("name", ["fx_se_k23", "fx_pe_k23", "fx_il_k23", "fx_edge", "fx_qual_veto"])
 def test_cli_small_batches_and_thread_flag(name, lanes, tmp_path, monkeypatch):
     # output must not depend on the batch size (the reference's is 512*T, main.cpp:441), nor on whether the batches in flight
     # run in slot lanes (a context per slot, kernels of consecutive batches side by side) or one after the other in one context

@@ -24,13 +24,14 @@ def _reads(d, want, oracle):
 
 
 @pytest.mark.parametrize("double", [False, True], ids=["as_built", "with_class_D"])
-@pytest.mark.parametrize("name", ["se_k23", "pe_k23", "il_k23", "skew", "k11", "k32", "varlen", "polya_k23", "pe_151", "pe_160_k15", "se_151", "k31_mc8", "nrich", "pe_var", "k15"])
+@pytest.mark.parametrize("name", ["se_k23", "pe_k23", "il_k23", "skew", "k11", "k32", "varlen", "polya_k23", "pe_151", "pe_160_k15", "se_151", "k31_mc8", "nrich", "pe_var", "k15",
+                                  "qv_mixed_pe/high", "qv_dense_mfk2/high"])
 def test_model_of_the_early_finish_agrees_with_the_oracle(oracle, name, double):
     d = datasets.make(name)
     k, mfk = d["k"], d["mfk"]
     T = oracle.Table(k, len(d["keys"]))
     T.put_many(d["keys"], d["counts"])
-    P = oracle.make_params(k, mfk, d["rate"], b"H")
+    P = oracle.make_params(k, mfk, d["rate"], d.get("badq", b"H"))
     want = datasets.run_oracle(oracle, d)
     ret, l, m, h = want[:4]
     seqs, mate, out = _reads(d, want, oracle)

@@ -68,3 +68,29 @@ def test_oracle_dump_loader_equals_reference_on_quirky_dumps(oracle, seed, tmp_p
                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
         res.append((p.returncode, p.stderr, open(os.path.join(od, "a.cor.fq"), "rb").read()))
     assert res[0][0] == 0 and res[0] == res[1]
+
+
+@pytest.mark.parametrize("name", ["qv_pair/straddle", "qv_ends/straddle", "qv_dense_mfk2/straddle", "qv_dense_mfk1/straddle", "qv_mixed_pe/straddle",
+                                  "qv_mixed_il/straddle", "qv_lengths/straddle", "qv_pair_k32/straddle", "qv_mixed_pe/fasta"])
+def test_oracle_cli_equals_reference_where_qualities_decide(oracle, name, tmp_path):
+    """The qv_ data sets (tests/datasets.py) as files, -maxcorK as the data set says: the GPU tests of the vetoes lean on the
+    oracle exactly here.  (FASTA with -t 2: the reference's -t 1 loop does not survive input without qualities.)"""
+    import datasets
+    if not os.path.exists(oracle.REF_BIN):
+        pytest.skip("oracle/_ref not built (needs /root/reference)")
+    d = str(tmp_path)
+    ds = datasets.for_cli(datasets.make(name))
+    if "lengths" in name:   # (1023 bases and a newline do not fit the reference's line buffer: those reads lose their last base)
+        assert sum(len(r) == 1023 for r in ds["seqs1"]) >= 10
+        ds = dict(ds, seqs1=[r[:1022] for r in ds["seqs1"]], quals1=[q[:1021] + q[-1:] if len(q) == 1023 else q for q in ds["quals1"]])
+    args = datasets.write_cli_case(ds, d) + (["-t", "2"] if ds["fasta"] else [])
+    res = []
+    for tag, binary in (("ref", oracle.REF_BIN), ("ora", oracle.CLI_BIN)):
+        od = os.path.join(d, tag)
+        os.makedirs(od)
+        p = subprocess.run([binary] + args + ["-od", od], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        res.append((p.returncode, p.stderr, {f: open(os.path.join(od, f), "rb").read() for f in sorted(os.listdir(od))}))
+    assert res[0][0] == 0 and res[0][2] and res[0] == res[1]
+    assert ds["fasta"] or b"Bad quality threshold is 'H'" in res[0][1], res[0][1]   # (datasets.for_cli: the bytes do straddle it)
+    before = b"".join(open(os.path.join(d, f), "rb").read() for f in sorted(os.listdir(d)) if f.startswith("reads"))
+    assert b"".join(res[0][2].values()) != before   # (something was corrected)

@@ -85,7 +85,7 @@ def _expect(d):
     k, mfk = d["k"], d["mfk"]
     T = po.Table(k, len(d["keys"]))
     T.put_many(d["keys"], d["counts"])
-    P = po.make_params(k, mfk, d["rate"], b"H")
+    P = po.make_params(k, mfk, d["rate"], d.get("badq", b"H"))
     seqs, mate = _all_reads(d)
     strong, info = M.front_end(P, T, seqs, k)
     out = []
@@ -129,7 +129,7 @@ def _run(d, monkeypatch, env=None):
         monkeypatch.delenv(kk)
     try:
         ctx.table_build(d["keys"], d["counts"])
-        ctx.set_run_params(d["rate"], b"H")
+        ctx.set_run_params(d["rate"], d.get("badq", b"H"))
         a, off = po.pack_reads(d["seqs1"])
         qa, _ = po.pack_reads(d["quals1"])
         arenas = [a]
@@ -301,7 +301,7 @@ def _planted_as_made(plan, d):
     po = _po()
     T = po.Table(d["k"], len(d["keys"]))
     T.put_many(d["keys"], d["counts"])
-    P = po.make_params(d["k"], d["mfk"], d["rate"], b"H")
+    P = po.make_params(d["k"], d["mfk"], d["rate"], d.get("badq", b"H"))
     k = plan.k
     for j, (r, subs) in enumerate(zip(plan.reads, plan.subs)):
         c = po.kmer_counts(P, T, r)
@@ -511,7 +511,7 @@ def _data_case(name):
     return d, exp, want
 
 
-@pytest.mark.parametrize("name", ["se_k23", "pe_k23", "il_k23", "skew", "k11", "k32", "pe_151", "pe_160_k15", "polya_k23", "k15"])
+@pytest.mark.parametrize("name", ["se_k23", "pe_k23", "il_k23", "skew", "k11", "k32", "pe_151", "pe_160_k15", "polya_k23", "k15", "qv_mixed_pe/high"])
 def test_routes_of_the_data_sets_equal_the_model(monkeypatch, name):
     d, exp, want = _data_case(name)
     n = len(exp)
