@@ -268,6 +268,37 @@ int rc_weak_profile_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_
  * No reference counterpart: the dormant fields of Reads.h:20,371-372,396-412. */
 int rc_weak_profile_into(rc_ctx *ctx, int slot, rc_read_weak *out, int32_t min_count);
 
+/* ---- per-read k-mer depth: the quartiles of every read's k-mer counts ----------------------------------------------------------
+ * What digital normalisation and depth-aware filters ask of every read (Trinity's in-silico normalisation, khmer's
+ * normalize-by-median): the median abundance of its k-mers.  For one read of L bases, at the context's k, against the
+ * context's table: window i (0 <= i <= L - k; none if L < k) is VALID exactly as for rc_read_weak above, and a valid window's
+ * count is GetCount of its canonical k-mer (Store.h:59-66), 0 for a k-mer the table does not hold -- a table loaded from a dump
+ * written with a lower count bound (jellyfish dump -L 2) holds no k-mer seen once.  With n the number of valid windows and
+ * c[0] <= ... <= c[n-1] their counts in ascending order:
+ *   valid   n
+ *   q1      c[(n - 1) / 4]
+ *   median  c[(n - 1) / 2]
+ *   q3      c[3 * (n - 1) / 4]      (integer division: lower quantiles, values that occur in the read)
+ * and four zeros for n == 0.  q1 <= median <= q3.  Exact integer arithmetic: no floats, no sampling, no histogram bins.
+ * Nothing is trimmed, dropped or reordered: the numbers only annotate.  No reference counterpart. */
+typedef struct { int32_t valid, q1, median, q3; } rc_read_depth;   /* 16 bytes per read */
+/* The reads of an arena in HBM as they are (call it behind rc_correct_device for the corrected ones): d_out[r] for each of the
+ * n_reads reads (read r the NUL-terminated string at d_off[r]; d_off has n_reads + 1 entries).  Asynchronous on the context's
+ * stream, like rc_weak_profile_device (rc_sync() to wait).  Needs a table; d_seq is never written, may start at any byte, and
+ * may be read in aligned 4-byte pieces up to 15 bytes in front of its first and behind its last byte.  An offset pair that
+ * leaves the arena describes no read and gives four zeros.  max_read_len is only checked: the kernel packs reads into its
+ * tiles by their own lengths, and a read of more than 1 023 bases -- which max_read_len promised not to exist -- gives four
+ * zeros.  RC_STATUS_ARG: a null pointer with n_reads > 0, an arena of 4 GiB or more, max_read_len above the library's 1 023
+ * bases; RC_STATUS_STATE: no table.  rc_profile_get's kernel 7 times it. */
+int rc_read_depth_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_off, uint32_t n_reads, uint64_t nbytes,
+                         int32_t max_read_len, rc_read_depth *d_out);
+/* One-shot, as rc_weak_profile_into and under the same rules: the NEXT batch submitted into `slot` also takes the depth of its
+ * corrected reads, on the GPU behind its last correction kernel; out[total] (indexed like ret / l / m / h) holds them when
+ * that batch's wait returns success.  The submit consumes the registration whether it succeeds or not; out == NULL withdraws;
+ * a page-locked `out` is written by DMA, any other by the wait that succeeds.  Both registrations may be armed on one submit.
+ * Without one a submit launches, copies and allocates nothing for it.  RC_STATUS_ARG: a bad slot; RC_STATUS_STATE: no table. */
+int rc_read_depth_into(rc_ctx *ctx, int slot, rc_read_depth *out);
+
 /* ---- duplicate census: how many reads / pairs are exact copies of one another, before and after correction ------------------
  * A UNIT is a read (mode 0) or a pair (mode 1: read r of the first half and read r of the second; mode 2: reads 2u and 2u + 1 --
  * the mates of the correction report).  Two units are duplicates when their base strings are byte for byte equal: equal
@@ -669,7 +700,7 @@ int rc_profile_correct_counters(rc_ctx *ctx, uint64_t *reads_listed, uint64_t *g
  * (MAX_TRIAL, ErrorCorrection.cpp:7; the straggler of tools/find_straggler.py).  NULL switches it off. */
 int rc_profile_read_rounds(rc_ctx *ctx, int32_t *d_rounds);
 /* kernel 0 = probe, 1 = threshold, 2 = correct, 3 = isolated substitutions, 4 = weak-k-mer profile, 5 = the trust profile's
- * planes, 6 = its accumulate and column sums; accumulated since the last reset */
+ * planes, 6 = its accumulate and column sums, 7 = per-read k-mer depth; accumulated since the last reset */
 int rc_profile_get(rc_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
 int rc_profile_reset(rc_ctx *ctx);
 

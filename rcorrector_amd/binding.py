@@ -19,6 +19,7 @@ ABI_SYMBOLS = [
     "rc_recount_begin", "rc_recount_add", "rc_recount_add_device", "rc_recount_follow", "rc_recount_finish",
     "rc_change_report_begin", "rc_change_report_get", "rc_change_report_end",
     "rc_weak_profile_device", "rc_weak_profile_into",
+    "rc_read_depth_device", "rc_read_depth_into",
     "rc_dup_census_begin", "rc_dup_census_get", "rc_dup_census_end", "rc_read_keys_device", "rc_dup_census_merge",
     "rc_trust_profile_device", "rc_trust_profile_begin", "rc_trust_profile_get", "rc_trust_profile_end",
     "rc_mate_overlap_device", "rc_mate_overlap_begin", "rc_mate_overlap_get", "rc_mate_overlap_end",
@@ -224,6 +225,8 @@ def load_library():
     L.rc_change_report_end.argtypes = [vp]
     L.rc_weak_profile_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, vp]
     L.rc_weak_profile_into.argtypes = [vp, C.c_int, vp, C.c_int32]
+    L.rc_read_depth_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, vp]
+    L.rc_read_depth_into.argtypes = [vp, C.c_int, vp]
     L.rc_dup_census_begin.argtypes = [vp]
     L.rc_dup_census_get.argtypes = [vp, C.c_uint32, C.POINTER(_DupCensus)]
     L.rc_dup_census_end.argtypes = [vp]
@@ -528,6 +531,32 @@ class Context:
     def weak_profile_withdraw(self, slot):
         """rc_weak_profile_into(out = NULL): the next batch of `slot` is not profiled after all"""
         self._ck(self._L.rc_weak_profile_into(self._h, int(slot), None, 1))
+
+    # ---- per-read k-mer depth: valid windows and the quartiles of their counts ----
+    def read_depth_device(self, d_seq, d_off, n_reads, nbytes, max_read_len, d_out):
+        """rc_read_depth_device: the reads of an arena in HBM as they are; d_out: device memory for n_reads x 4 int32
+        (valid, q1, median, q3: rc_read_depth).  Asynchronous: sync() to wait."""
+        self._ck(self._L.rc_read_depth_device(self._h, _ptr(d_seq), _ptr(d_off), n_reads, nbytes, int(max_read_len), _ptr(d_out)))
+
+    def read_depth_into(self, slot, total_reads, out=None):
+        """rc_read_depth_into: the next batch submitted into `slot` (correct_batch: slot 0) also takes the k-mer depth of its
+        corrected reads.  Returns a page-locked (total_reads, 4) int32 array -- columns valid, q1, median, q3, rows indexed like
+        ret / l / m / h -- that the batch's wait fills (out: a C-contiguous int32 array of that shape to fill instead, e.g. a
+        pageable one).  One shot: every submit consumes the registration."""
+        total_reads = int(total_reads)
+        if out is None:
+            out = self.host_array(total_reads * 4, dtype=np.int32).reshape(total_reads, 4)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.shape == (total_reads, 4)):
+            raise TypeError("out must be a C-contiguous int32 numpy array of shape (total_reads, 4)")
+        self._ck(self._L.rc_read_depth_into(self._h, int(slot), out.ctypes.data))
+        if not hasattr(self, "_depth_out"):
+            self._depth_out = {}
+        self._depth_out[int(slot)] = out   # (the library writes it until the batch's wait returns)
+        return out
+
+    def read_depth_withdraw(self, slot):
+        """rc_read_depth_into(out = NULL): the next batch of `slot` has its depth not taken after all"""
+        self._ck(self._L.rc_read_depth_into(self._h, int(slot), None))
 
     # ---- duplicate census: exact copies among the reads / pairs, before and after correction ----
     def dup_census_begin(self):

@@ -48,6 +48,15 @@ struct rc_slot_out {
     size_t *n_fix = nullptr;
 };
 
+// 16 bytes per read that a batch in flight computes behind its last correction kernel for a one-shot registration: the
+// caller's array (nullptr: none asked for), whether it is page-locked, the values in HBM, and their staging where it is not
+struct rc_slot_payload {
+    void *out = nullptr;
+    bool pinned = false;
+    rc_dbuf d;
+    rc_hbuf p;
+};
+
 // one batch in flight on the asynchronous slot transports
 struct rc_slot {
     rc_slot_kind kind = RC_SLOT_NONE;
@@ -69,12 +78,9 @@ struct rc_slot {
     rc_slot_out out;
     rc_dbuf d_packed, d_exc, d_fix;
     rc_hbuf p_in, p_fix, p_nfix;
-    // weak-k-mer profile of the batch in flight (rc_weak_profile_into): the caller's array (nullptr: none asked for), the 16
-    // bytes per read in HBM, and their staging where the caller's array is not page-locked
-    void *weak_out = nullptr;
-    bool weak_pinned = false;
-    rc_dbuf d_weak;
-    rc_hbuf p_weak;
+    // the per-read payloads of the batch in flight, 16 bytes per read each: its weak-k-mer profile (rc_weak_profile_into) and
+    // its k-mer depth (rc_read_depth_into)
+    rc_slot_payload weak, depth;
     // what the batch observers staged for the batch in flight, until its wait accepts it (a packed / resident batch that did
     // not fit its fix list comes again, and only then counts)
     rc_batch_observed obs;

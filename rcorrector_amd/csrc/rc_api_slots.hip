@@ -16,14 +16,24 @@ template <class Entry>
 static int in_slot_lane(rc_ctx *c, int slot, bool submit, Entry entry)
 {
     if (!c || slot < 0 || slot >= RC_MAX_SLOTS) return RC_ERR_ARG;
-    // a submit takes the slot's weak-profile registration (rc_weak_profile_into) with it, whatever becomes of the submit
+    // a submit takes the slot's registrations (rc_weak_profile_into, rc_read_depth_into) with it, whatever becomes of the submit
     rc_ctx::rc_weak_reg weak;
-    if (submit) std::swap(weak, c->weak_reg[slot]);
+    rc_ctx::rc_depth_reg depth;
+    if (submit) {
+        std::swap(weak, c->weak_reg[slot]);
+        std::swap(depth, c->depth_reg[slot]);
+    }
     rc_ctx *ln = rc_slot_lane(c, slot, submit, submit);
     if (!ln) return RC_ERR_HIP;
-    if (submit) ln->weak_cur = weak;
+    if (submit) {
+        ln->weak_cur = weak;
+        ln->depth_cur = depth;
+    }
     const int rc = entry(static_cast<rc_ctx_full *>(ln), ln == c ? slot : 0);
-    if (submit) ln->weak_cur = rc_ctx::rc_weak_reg();  // (a submit that returned in front of slot_download: nothing stays behind)
+    if (submit) {  // (a submit that returned in front of slot_download: nothing stays behind)
+        ln->weak_cur = rc_ctx::rc_weak_reg();
+        ln->depth_cur = rc_ctx::rc_depth_reg();
+    }
     if (rc && ln != c) rc_lane_error(c, ln);
     return rc;
 }
@@ -38,7 +48,7 @@ static int slot_acquire(rc_ctx_full *ctx, int slot, const char *name, const char
         rc_set_error(ctx, "%s: slot %d still holds a batch (%s first)", name, slot, wait_hint);
         return RC_ERR_STATE;
     }
-    sl.weak_out = nullptr;  // (slot_download sets it for a batch that has a weak-profile registration)
+    sl.weak.out = sl.depth.out = nullptr;  // (slot_download sets them for a batch that has the registration)
     sl.obs.reset();         // (rc_correct_observed stages into it what the armed observers take of the batch)
     *out = &sl;
     return RC_OK;
@@ -127,10 +137,35 @@ static int slot_fix_list_target(rc_ctx_full *ctx, const rc_slot &sl, uint32_t **
     return RC_OK;
 }
 
+// A per-read payload (rc_api_internal.h: rc_slot_payload), the three steps of its way.  reserve: the registration's array into
+// the slot, with room for the values in HBM and, where the array is not page-locked, in the slot's staging; nothing for out ==
+// nullptr.  download: the 16 bytes per read on the download stream, into the array or the staging.  back: a wait that succeeds
+// hands over what went to the staging.
+static int payload_reserve(rc_ctx_full *ctx, rc_slot_payload &pl, void *out, size_t total)
+{
+    pl.out = out;
+    if (!out) return RC_OK;
+    if (const int rc = rc_dbuf_reserve(ctx, &pl.d, total * 16)) return rc;
+    pl.pinned = rc_is_pinned(out, total * 16);
+    return pl.pinned ? (int)RC_OK : rc_hbuf_reserve(ctx, &pl.p, total * 16);
+}
+
+static int payload_download(rc_ctx_full *ctx, const rc_slot_payload &pl, size_t total)
+{
+    if (pl.out) RC_CHECK_HIP(ctx, hipMemcpyAsync(pl.pinned ? pl.out : pl.p.p, pl.d.p, total * 16, hipMemcpyDeviceToHost, ctx->s_d2h));
+    return RC_OK;
+}
+
+static void payload_back(const rc_slot_payload &pl, size_t total)
+{
+    if (pl.out && !pl.pinned) memcpy(pl.out, pl.p.p, total * 16);
+}
+
 // Behind the batch's last kernel: what `first` queues on the download stream (the arena, the fix count), then ret / l / m / h to
 // sl.out or the slot's staging.  one_copy: where the caller's four arrays are one block, as the device's are, one copy instead
 // of four.  A batch submitted with a weak-profile registration (rc_weak_profile_into: ctx->weak_cur) has its corrected arena
-// profiled first, behind its last kernel on its own stream, and the 16 bytes per read come down with the results.
+// profiled first, behind its last kernel on its own stream, and the 16 bytes per read come down with the results; one with a
+// depth registration (rc_read_depth_into: ctx->depth_cur) has its k-mer depth taken the same way.
 template <class First>
 static int slot_download(rc_ctx_full *ctx, rc_slot &sl, bool one_copy, First first)
 {
@@ -138,22 +173,23 @@ static int slot_download(rc_ctx_full *ctx, rc_slot &sl, bool one_copy, First fir
     const rc_slot_out &o = sl.out;
     const int32_t *d_res = (const int32_t *)sl.d_res.p;
     const rc_ctx::rc_weak_reg weak = ctx->weak_cur;
+    const rc_ctx::rc_depth_reg depth = ctx->depth_cur;
     ctx->weak_cur = rc_ctx::rc_weak_reg();
-    sl.weak_out = weak.out;
-    if (sl.weak_out) {
-        int rc;
-        if ((rc = rc_dbuf_reserve(ctx, &sl.d_weak, total * 16))) return rc;
-        sl.weak_pinned = rc_is_pinned(sl.weak_out, total * 16);
-        if (!sl.weak_pinned && (rc = rc_hbuf_reserve(ctx, &sl.p_weak, total * 16))) return rc;
-        if ((rc = rc_launch_weak_profile(ctx, (const uint8_t *)sl.d_seq.p, sl.arena_bytes, (const uint32_t *)sl.d_off.p, (uint32_t)total,
-                                         weak.min_count, &ctx->weak_planes, sl.d_weak.p)))
-            return rc;
-    }
+    ctx->depth_cur = rc_ctx::rc_depth_reg();
+    sl.depth.out = nullptr;
+    int prc;
+    if ((prc = payload_reserve(ctx, sl.weak, weak.out, total))) return prc;
+    if (sl.weak.out && (prc = rc_launch_weak_profile(ctx, (const uint8_t *)sl.d_seq.p, sl.arena_bytes, (const uint32_t *)sl.d_off.p, (uint32_t)total,
+                                                     weak.min_count, &ctx->weak_planes, sl.weak.d.p)))
+        return prc;
+    if ((prc = payload_reserve(ctx, sl.depth, depth.out, total))) return prc;
+    if (sl.depth.out && (prc = rc_launch_read_depth(ctx, (const uint8_t *)sl.d_seq.p, sl.arena_bytes, (const uint32_t *)sl.d_off.p, (uint32_t)total, sl.depth.d.p)))
+        return prc;
     RC_CHECK_HIP(ctx, hipEventRecord(sl.e_k, ctx->stream));
     RC_CHECK_HIP(ctx, hipStreamWaitEvent(ctx->s_d2h, sl.e_k, 0));
     if (const int rc = first()) return rc;
-    if (sl.weak_out)
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(sl.weak_pinned ? sl.weak_out : sl.p_weak.p, sl.d_weak.p, total * 16, hipMemcpyDeviceToHost, ctx->s_d2h));
+    if ((prc = payload_download(ctx, sl.weak, total))) return prc;
+    if ((prc = payload_download(ctx, sl.depth, total))) return prc;
     if (!sl.res_pinned) {
         RC_CHECK_HIP(ctx, hipMemcpyAsync(sl.p_res.p, d_res, total * 16, hipMemcpyDeviceToHost, ctx->s_d2h));
     } else if (one_copy && o.l == o.ret + total && o.m == o.l + total && o.h == o.m + total) {
@@ -172,7 +208,8 @@ static int slot_download(rc_ctx_full *ctx, rc_slot &sl, bool one_copy, First fir
 static void slot_results_back(const rc_slot &sl)
 {
     const size_t total = sl.total_reads;
-    if (sl.weak_out && !sl.weak_pinned) memcpy(sl.weak_out, sl.p_weak.p, total * 16);
+    payload_back(sl.weak, total);
+    payload_back(sl.depth, total);
     if (sl.res_pinned) return;
     const int32_t *r = (const int32_t *)sl.p_res.p;
     memcpy(sl.out.ret, r, total * 4);

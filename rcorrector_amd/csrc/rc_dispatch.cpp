@@ -300,6 +300,22 @@ static void format_job(Run &R, Job &J)
         wsuf[s] += wk[gi].bad_suffix > 0;
         wnone[s] += L > 0 && wk[gi].uncovered == L;
     };
+    // -depth-tags / -depth: the reads of either mate (mode 2: the odd reads are the second mates) without a valid window, and the
+    // others by their median, the last bin holding every median of at least depth_max
+    const rc_read_depth *dp = R.depth_on ? J.depth.data() : nullptr;
+    const rc_read_depth *dtag = R.depth_tags ? dp : nullptr;
+    const size_t DS = dp ? S : 0, bins = (size_t)R.depth_max + 1;
+    std::vector<std::vector<uint64_t>> dhist(2 * DS);
+    std::vector<uint64_t> dnone(2 * DS, 0);
+    auto tally_depth = [&](size_t s, int mate, size_t gi) {
+        if (dp[gi].valid <= 0) {
+            ++dnone[2 * s + (size_t)mate];
+            return;
+        }
+        std::vector<uint64_t> &hgm = dhist[2 * s + (size_t)mate];
+        if (hgm.empty()) hgm.assign(bins, 0);
+        ++hgm[std::min<size_t>((size_t)dp[gi].median, bins - 1)];
+    };
     auto fmt = [&](size_t lo, size_t hi) {
         for (size_t s = lo; s < hi; ++s) {
             const size_t r0 = n * s / S, r1 = n * (s + 1) / S;
@@ -311,17 +327,22 @@ static void format_job(Run &R, Job &J)
                     tally(s, j->a, r, r);
                     if (j->mode == 1) tally(s, j->b, r, n + r);
                 }
+                if (dp) {
+                    tally_depth(s, j->mode == 2 ? (int)(r & 1) : 0, r);
+                    if (j->mode == 1) tally_depth(s, 1, n + r);
+                }
             }
             cor[s] = c;
             o1[s].reserve((r1 - r0) * 300);
             for (size_t r = r0; r < r1; ++r) {
-                put_record(o1[s], j->a, r, j->fastq, j->ret[r], j->l[r], j->m[r], j->h[r], wk ? wk + r : nullptr);
-                if (alternate) put_record(o1[s], j->b, r, j->fastq, j->ret[n + r], j->l[n + r], j->m[n + r], j->h[n + r], wk ? wk + n + r : nullptr);
+                put_record(o1[s], j->a, r, j->fastq, j->ret[r], j->l[r], j->m[r], j->h[r], wk ? wk + r : nullptr, dtag ? dtag + r : nullptr);
+                if (alternate)
+                    put_record(o1[s], j->b, r, j->fastq, j->ret[n + r], j->l[n + r], j->m[n + r], j->h[n + r], wk ? wk + n + r : nullptr, dtag ? dtag + n + r : nullptr);
             }
             if (j->mode == 1 && !alternate) {
                 o2[s].reserve((r1 - r0) * 300);
                 for (size_t r = r0; r < r1; ++r)
-                    put_record(o2[s], j->b, r, j->fastq, j->ret[n + r], j->l[n + r], j->m[n + r], j->h[n + r], wk ? wk + n + r : nullptr);
+                    put_record(o2[s], j->b, r, j->fastq, j->ret[n + r], j->l[n + r], j->m[n + r], j->h[n + r], wk ? wk + n + r : nullptr, dtag ? dtag + n + r : nullptr);
             }
         }
     };
@@ -333,6 +354,16 @@ static void format_job(Run &R, Job &J)
         J.weak_prefix += wpre[s];
         J.weak_suffix += wsuf[s];
         J.weak_nosolid += wnone[s];
+    }
+    for (int mate = 0; mate < 2; ++mate) {
+        J.depth_hist[mate].assign(dp ? bins : 0, 0);
+        J.depth_novalid[mate] = 0;
+        J.depth_reads[mate] = !dp ? 0 : j->mode == 1 ? n : j->mode == 2 ? (n + 1 - (size_t)mate) / 2 : mate == 0 ? n : 0;
+        for (size_t s = 0; s < DS; ++s) {
+            J.depth_novalid[mate] += dnone[2 * s + (size_t)mate];
+            const std::vector<uint64_t> &hgm = dhist[2 * s + (size_t)mate];
+            for (size_t d = 0; d < hgm.size(); ++d) J.depth_hist[mate][d] += hgm[d];
+        }
     }
     if (gz1 || gz2) {  // deflate every slice into its own gzip member, in parallel
         std::vector<OutBuf> z1(S), z2(S);
@@ -424,8 +455,14 @@ static void worker_body(Run &R, int wk)
         j->h.assign(total, 0);
         // -weak-ends: the batch about to be submitted into this worker's slot also profiles its corrected reads (one shot: a batch
         // that is submitted again registers again); called with the GPU's submit lock held, in front of the submit
+        // -depth-tags / -depth: the same for the corrected reads' k-mer depth (rc_read_depth_into)
         if (R.weak_ends) j->weak.assign(total, rc_read_weak());
-        auto arm_weak = [&]() { return R.weak_ends ? rc_weak_profile_into(ctx[g], slot, j->weak.data(), R.weak_min) : 0; };
+        if (R.depth_on) j->depth.assign(total, rc_read_depth());
+        auto arm_per_read = [&]() {
+            int arc = R.weak_ends ? rc_weak_profile_into(ctx[g], slot, j->weak.data(), R.weak_min) : 0;
+            if (!arc && R.depth_on) arc = rc_read_depth_into(ctx[g], slot, j->depth.data());
+            return arc;
+        };
         bool resident_done = false;
         int rrc = 0;
         double tq1 = tp0;
@@ -472,7 +509,7 @@ static void worker_body(Run &R, int wk)
                 rb.fix_cap = cap;
                 {
                     std::lock_guard<std::mutex> lk(submit_mu[(size_t)g]);
-                    if (!(rrc = arm_weak())) rrc = rc_submit_resident(ctx[g], &rb, slot);
+                    if (!(rrc = arm_per_read())) rrc = rc_submit_resident(ctx[g], &rb, slot);
                 }
                 if (!rrc) rrc = rc_wait_resident(ctx[g], slot);
                 // more substitutions than the list has room for (a heavily corrected tail batch: the list is sized for one fix
@@ -630,13 +667,13 @@ static void worker_body(Run &R, int wk)
             pb.fix_cap = cap;
             {
                 std::lock_guard<std::mutex> lk(submit_mu[(size_t)g]);
-                if (!(rc = arm_weak())) rc = rc_submit_packed(ctx[g], &pb, slot);
+                if (!(rc = arm_per_read())) rc = rc_submit_packed(ctx[g], &pb, slot);
             }
             if (!rc) rc = rc_wait_packed(ctx[g], slot);
             if (rc == RC_STATUS_NOSPACE) {  // (see the resident path) the arenas are untouched: once more, as bytes
                 {
                     std::lock_guard<std::mutex> lk(submit_mu[(size_t)g]);
-                    if (!(rc = arm_weak())) rc = rc_submit(ctx[g], &rb, slot);
+                    if (!(rc = arm_per_read())) rc = rc_submit(ctx[g], &rb, slot);
                 }
                 if (!rc) rc = rc_wait(ctx[g], slot);
                 pb.n_fix = 0;
@@ -657,7 +694,7 @@ static void worker_body(Run &R, int wk)
             {   // upload + kernels + download are queued here; the wait below overlaps with the other
                 // workers' packing, submitting and formatting
                 std::lock_guard<std::mutex> lk(submit_mu[(size_t)g]);
-                if (!(rc = arm_weak())) rc = rc_submit(ctx[g], &rb, slot);
+                if (!(rc = arm_per_read())) rc = rc_submit(ctx[g], &rb, slot);
             }
             if (!rc) rc = rc_wait(ctx[g], slot);
         }
@@ -762,6 +799,12 @@ for (;;) {
     R.weak_prefix += j->weak_prefix;
     R.weak_suffix += j->weak_suffix;
     R.weak_nosolid += j->weak_nosolid;
+    for (int mate = 0; mate < 2 && R.depth_on; ++mate) {
+        R.depth_reads[mate] += j->depth_reads[mate];
+        R.depth_novalid[mate] += j->depth_novalid[mate];
+        if (R.depth_hist[mate].size() < j->depth_hist[mate].size()) R.depth_hist[mate].resize(j->depth_hist[mate].size(), 0);
+        for (size_t d = 0; d < j->depth_hist[mate].size(); ++d) R.depth_hist[mate][d] += j->depth_hist[mate][d];
+    }
     bool retire = false;
     {
         std::lock_guard<std::mutex> lk(mu);

@@ -37,6 +37,13 @@ struct Run {
     bool weak_ends = false;
     int weak_min = 1;
     uint64_t weak_prefix = 0, weak_suffix = 0, weak_nosolid = 0;
+    // -depth-tags / -depth FILE: every batch also asks for its corrected reads' k-mer depth (rc_read_depth_into); -depth-tags puts
+    // kdepth=Q1:MED:Q3 on the records, and either way the writer adds up, per mate, the reads, those without a valid k-mer window
+    // and the others by their median (depth_hist[mate][d], d = depth_max: that or more)
+    bool depth_on = false, depth_tags = false;
+    uint32_t depth_max = 10000;
+    uint64_t depth_reads[2] = {0, 0}, depth_novalid[2] = {0, 0};
+    std::vector<uint64_t> depth_hist[2];
     bool recount_host = false;  // -histo-after with several GPUs: the workers hand every corrected batch's bases to ctx[0]'s recount session
     std::vector<ReadFile> files, mates;
     std::vector<rc_ctx *> ctx;                // one per GPU (the table is replicated)

@@ -166,6 +166,37 @@ bool write_dup_census(const char *path, const rc_dup_census &D, uint32_t max_bin
     return fclose(fp) == 0 && ok;
 }
 
+bool write_depth_report(const char *path, int k, const uint64_t reads[2], const uint64_t novalid[2], const std::vector<uint64_t> hist[2], bool two_mates)
+{
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return false;
+    typedef unsigned long long ull;
+    const int mates = two_mates ? 2 : 1;
+    bool ok = fprintf(fp, "k\t%d\n", k) > 0;
+    for (int m = 0; m < mates; ++m) ok = ok && fprintf(fp, "reads\t%d\t%llu\n", m + 1, (ull)reads[m]) > 0;
+    for (int m = 0; m < mates; ++m) ok = ok && fprintf(fp, "novalid\t%d\t%llu\n", m + 1, (ull)novalid[m]) > 0;
+    for (size_t d = 0; d < std::max(hist[0].size(), hist[1].size()) && ok; ++d) {
+        const uint64_t h1 = d < hist[0].size() ? hist[0][d] : 0, h2 = d < hist[1].size() ? hist[1][d] : 0;
+        if (!h1 && !(two_mates && h2)) continue;
+        ok = (two_mates ? fprintf(fp, "median\t%zu\t%llu\t%llu\n", d, (ull)h1, (ull)h2) : fprintf(fp, "median\t%zu\t%llu\n", d, (ull)h1)) > 0;
+    }
+    return fclose(fp) == 0 && ok;
+}
+
+size_t depth_median_of_medians(const std::vector<uint64_t> hist[2])
+{
+    uint64_t n = 0;
+    for (int m = 0; m < 2; ++m)
+        for (uint64_t c : hist[m]) n += c;
+    if (!n) return 0;
+    uint64_t seen = 0;
+    for (size_t d = 0; d < std::max(hist[0].size(), hist[1].size()); ++d) {
+        seen += (d < hist[0].size() ? hist[0][d] : 0) + (d < hist[1].size() ? hist[1][d] : 0);
+        if (seen > (n - 1) / 2) return d;
+    }
+    return 0;
+}
+
 void add_trust_profile(rc_trust_profile &to, const rc_trust_profile &from)
 {
     to.reads[0] += from.reads[0];

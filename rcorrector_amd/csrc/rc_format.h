@@ -2,6 +2,7 @@
 // the text, quality bits and fixes of the one-pass path, and the output records.
 //   record       Reads.h:224-266,360-421    4 lines in; "<id> l:%d m:%d h:%d[ cor| unfixable_error]" out
 //   -weak-ends   Reads.h:396-412            " bad_prefix=%d" / " bad_suffix=%d" behind " cor": the reference's dormant tags
+//   -depth-tags  (no reference counterpart) " kdepth=Q1:MED:Q3" behind those: the quartiles of the read's k-mer counts
 //   transcript   ErrorCorrection.cpp:686-689,759-770,856-857,1088-1094,1590-1597 (-verbose)
 #pragma once
 #include <emmintrin.h>
@@ -36,6 +37,9 @@ struct Job {
     std::vector<int32_t> tr_before, tr_after, tr_flags, tr_niter, tr_iter;  // -verbose only
     std::vector<rc_read_weak> weak;  // -weak-ends only: the corrected reads' profile, indexed like ret (rc_weak_profile_into)
     uint64_t weak_prefix = 0, weak_suffix = 0, weak_nosolid = 0;  // ... and the reads with a bad prefix / a bad suffix / no solid k-mer
+    std::vector<rc_read_depth> depth;  // -depth-tags / -depth only: the corrected reads' k-mer depth, indexed like ret (rc_read_depth_into)
+    std::vector<uint64_t> depth_hist[2];  // ... and per mate the reads by median (the last bin: -depth-max or more), all of its reads, those
+    uint64_t depth_reads[2] = {0, 0}, depth_novalid[2] = {0, 0};  // without a valid window
     bool resident = false;        // the batch's reads are arenas the k-mer counter kept in HBM (rc_submit_resident)
     int arena_a = 0, arena_b = 0;
     int gpu = -1;                 // the GPU that holds them (-1: any GPU may take the batch)
@@ -107,15 +111,17 @@ static inline char *put_int(char *p, int v)
 // stripped of its newline only when it is exactly as long as the sequence line (Reads.h:255-262).
 // wk (-weak-ends): the read's weak-k-mer profile -- the tags of the reference's dormant branch (Reads.h:396-412) follow " cor",
 // each only where its value is above 0; the unfixable branch (:389) has none.  nullptr: the record as without the flag.
+// dp (-depth-tags): the read's k-mer depth -- " kdepth=Q1:MED:Q3" last of all, on every record whose read has a valid window.
 template <class B>
-static inline void put_record(B &out, const Arena &A, size_t r, bool fastq, int cor, int l, int m, int h, const rc_read_weak *wk = nullptr)
+static inline void put_record(B &out, const Arena &A, size_t r, bool fastq, int cor, int l, int m, int h, const rc_read_weak *wk = nullptr,
+                              const rc_read_depth *dp = nullptr)
 {
     uint32_t il, ql = 0;
     const char *id = A.line(r, 0, &il);
     const char *seq = A.sequence(r);
     const uint32_t sl = A.off[r + 1] - A.off[r] - 1;
     const char *q = fastq ? A.line(r, 3, &ql) : nullptr;
-    const size_t need = (size_t)il + sl + ql + 96 + (wk ? 48 : 0);
+    const size_t need = (size_t)il + sl + ql + 96 + (wk ? 48 : 0) + (dp ? 48 : 0);
     const size_t at = out.size();
     out.resize(at + need);
     char *p = out.data() + at;
@@ -143,6 +149,14 @@ static inline void put_record(B &out, const Arena &A, size_t r, bool fastq, int 
             memcpy(p, " bad_suffix=", 12);
             p = put_int(p + 12, wk->bad_suffix);
         }
+    }
+    if (dp && dp->valid > 0) {
+        memcpy(p, " kdepth=", 8);
+        p = put_int(p + 8, dp->q1);
+        *p++ = ':';
+        p = put_int(p, dp->median);
+        *p++ = ':';
+        p = put_int(p, dp->q3);
     }
     *p++ = '\n';
     memcpy(p, seq, sl);
@@ -193,6 +207,12 @@ void add_trust_profile(rc_trust_profile &to, const rc_trust_profile &from);
 std::string mate_overlap_text(const rc_mate_overlap &M);
 bool write_mate_overlap(const char *path, const rc_mate_overlap &M);
 void add_mate_overlap(rc_mate_overlap &to, const rc_mate_overlap &from);
+// the k-mer depth report (rcorrector_amd.h: rc_read_depth, the corrected reads' medians) as tab-separated text: k <k> / reads
+// <mate 1|2> <n> / novalid <mate> <n> (reads without a valid k-mer window: they have no median) / median <d> <reads of mate 1>
+// [<reads of mate 2>], a line per d that some read has; the line of d = hist[m].size() - 1: that or more.  Mate 2 only with two_mates.
+// depth_median_of_medians: the lower median of the reads' medians over both mates (bin index; the last bin: that or more), 0 of none
+bool write_depth_report(const char *path, int k, const uint64_t reads[2], const uint64_t novalid[2], const std::vector<uint64_t> hist[2], bool two_mates);
+size_t depth_median_of_medians(const std::vector<uint64_t> hist[2]);
 // GetBadQuality's two histograms over the records of one block (main.cpp:88-128), at most `room` of them
 void quality_histograms(const Block &b, int lpr, size_t room, std::vector<int32_t> &fh, std::vector<int32_t> &lh, int *total);
 

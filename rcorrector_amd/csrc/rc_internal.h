@@ -112,7 +112,7 @@ struct rc_kernel_timer {
     uint64_t launches = 0;
 };
 
-enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_TRUST_PLANES = 5, RC_T_TRUST = 6, RC_T_COUNT };
+enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_TRUST_PLANES = 5, RC_T_TRUST = 6, RC_T_DEPTH = 7, RC_T_COUNT };
 
 struct rc_ctx {
     int device = 0;
@@ -202,6 +202,12 @@ struct rc_ctx {
     };
     rc_dbuf weak_planes;
     rc_weak_reg weak_reg[4], weak_cur;
+    // k-mer depth (rc_read_depth_device / rc_read_depth_into; kernel in rc_depth.hip): the registrations travel as the weak
+    // profile's do -- depth_reg per slot of this context's entry points, depth_cur in the context the batch runs in
+    struct rc_depth_reg {
+        void *out = nullptr;  // rc_read_depth[total]
+    };
+    rc_depth_reg depth_reg[4], depth_cur;
     // duplicate census (rc_dup_census_begin; kernels in rc_dups.hip).  In the context it was opened on (the batches of its slot
     // lanes add to it too: rc_home): the keys of every unit seen, version 0 = before and 1 = after correction, 16 bytes per
     // unit each, dup_n units of dup_cap; dup_gen counts the begins (keys a batch staged for one census never reach the next).
@@ -385,6 +391,10 @@ int rc_launch_report_commit(rc_ctx *ctx, const unsigned long long *d_staged, uns
 // rc_weak.hip: solid / weak bit planes of the arena into `planes` (grow-only), then d_out[r] = the rc_read_weak of read r
 int rc_launch_weak_profile(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int min_count, rc_dbuf *planes,
                            void *d_out);
+
+// rc_depth.hip: d_out[r] = the rc_read_depth of read r, one launch; a read whose offsets leave the arena, or of more than
+// RC_MAX_READ_LENGTH - 1 bases, gets four zeros
+int rc_launch_read_depth(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, void *d_out);
 
 // rc_weak.hip: the two bit planes alone (what rc_launch_weak_profile launches first): *solid / *weak point into `planes`,
 // *lead = the bytes between the 16-byte boundary the planes start at and d_seq.  rc_trust.hip: the planes of the arena at

@@ -35,6 +35,9 @@
 // -overlap FILE writes the mate-overlap report (rcorrector_amd.h: rc_mate_overlap; rc_format.h: write_mate_overlap): where mate 1
 // and the reverse complement of mate 2 cover the same bases, the bases they disagree on before and after correction -- resolved,
 // kept, introduced -- and the fragment lengths (-overlap-min / -overlap-mm: the shortest overlap and the most mismatches accepted).
+// -depth-tags tags every record whose corrected read has a valid k-mer window with kdepth=Q1:MED:Q3, the quartiles of its k-mers'
+// counts in the table (rcorrector_amd.h: rc_read_depth); -depth FILE writes the reads by median (rc_format.h: write_depth_report;
+// -depth-max: its last bin).  Either adds one line to stderr.
 #include <fcntl.h>
 #include <malloc.h>
 #include <sys/stat.h>
@@ -83,6 +86,14 @@ static void print_help()
             "\t\tnothing is trimmed; one more line on stderr counts the reads with a bad prefix, a bad suffix, and no such k-mer at all\n"
             "\t\t(every read counts there, unfixable ones included); not with -verbose\n"
             "\t-weak-min INT: with -weak-ends and -trust-by-pos, a k-mer counted fewer times than this in the table is weak (default: 1)\n"
+            "\t-depth-tags: tag every record whose corrected read has a valid k-mer window, last behind l:m:h, cor and the -weak-ends tags,\n"
+            "\t\twith kdepth=Q1:MED:Q3: the lower quartile, median and upper quartile of the counts its k-mers have in the table (exact lower\n"
+            "\t\tquantiles; a k-mer the table does not hold counts 0 -- with -c, whatever the dump left out); nothing is dropped, trimmed or\n"
+            "\t\treordered; one more line on stderr; not with -verbose\n"
+            "\t-depth STRING: also write the k-mer depth report, tab-separated text: k, per mate the reads and those without a valid k-mer\n"
+            "\t\twindow, and for every median that occurs the reads of mate 1 (and of mate 2 for -p / -i input) that have it; with -gpus\n"
+            "\t\tabove 1 the GPUs' batches are added up; the same line on stderr; not with -verbose\n"
+            "\t-depth-max INT: with -depth, reads with a median of this or more are counted in the last line (default: 10000)\n"
             "\t-dups STRING: also write the duplicate census, tab-separated text: the units (reads, or pairs for -1/-2 and -i input), the\n"
             "\t\tdistinct units before and after correction, and for every number of copies c the distinct units that occur c times,\n"
             "\t\tbefore and after; two units are copies when their bases are byte for byte equal (mate 1 with mate 1, mate 2 with\n"
@@ -115,7 +126,8 @@ int main(int argc, char **argv)
     int max_fix_per_k = 4, i;
     double wk = 0.95;
     const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr, *report = nullptr, *dups = nullptr, *trust = nullptr;
-    const char *overlap = nullptr;
+    const char *overlap = nullptr, *depth = nullptr;
+    long depth_max = 10000;
     int overlap_min = 30, overlap_mm = 10;
     long dups_max = 10000;
     long histo_max = 10000;
@@ -191,6 +203,12 @@ int main(int argc, char **argv)
             run.weak_ends = true;
         else if (!strcmp("-weak-min", argv[i]))
             run.weak_min = atoi(argv[++i]);
+        else if (!strcmp("-depth-tags", argv[i]))
+            run.depth_tags = true;
+        else if (!strcmp("-depth", argv[i]))
+            depth = argv[++i];
+        else if (!strcmp("-depth-max", argv[i]))
+            depth_max = atol(argv[++i]);
         else if (!strcmp("-packed", argv[i]))
             g_packed = true;
         else if (!strcmp("-h", argv[i])) {
@@ -203,6 +221,10 @@ int main(int argc, char **argv)
     }
     g_verbose = verbose;
     if (run.weak_ends && verbose) die("rcorrector: usage: -weak-ends cannot be combined with -verbose (the transcript's entry point takes no weak-k-mer profile)\n");
+    if ((run.depth_tags || depth) && verbose) die("rcorrector: usage: %s cannot be combined with -verbose (the transcript's entry point takes no k-mer depth)\n", run.depth_tags ? "-depth-tags" : "-depth");
+    if (depth_max < 1 || depth_max > (1l << 28)) die("rcorrector: usage: -depth-max must be 1..%ld\n", 1l << 28);
+    run.depth_on = run.depth_tags || depth;
+    run.depth_max = (uint32_t)depth_max;
     if (dups && verbose) die("rcorrector: usage: -dups cannot be combined with -verbose (small batches through the transcript's entry point: run the census without it)\n");
     if (trust && verbose) die("rcorrector: usage: -trust-by-pos cannot be combined with -verbose (small batches through the transcript's entry point: run the profile without it)\n");
     if (overlap && verbose) die("rcorrector: usage: -overlap cannot be combined with -verbose (small batches through the transcript's entry point: run the report without it)\n");
@@ -609,6 +631,18 @@ int main(int argc, char **argv)
     if (run.weak_ends)
         fprintf(stderr, "Weak ends (k-mers counted below %d): %llu reads with a bad prefix, %llu with a bad suffix, %llu without a solid k-mer\n", run.weak_min,
                 (unsigned long long)run.weak_prefix, (unsigned long long)run.weak_suffix, (unsigned long long)run.weak_nosolid);
+    if (run.depth_on) {
+        const uint64_t with = run.depth_reads[0] + run.depth_reads[1] - run.depth_novalid[0] - run.depth_novalid[1];
+        const uint64_t zero = (run.depth_hist[0].empty() ? 0 : run.depth_hist[0][0]) + (run.depth_hist[1].empty() ? 0 : run.depth_hist[1][0]);
+        const size_t mm = depth_median_of_medians(run.depth_hist);
+        fprintf(stderr, "K-mer depth: %llu reads with a valid k-mer window, %llu of them with a median of 0; the median of the reads' medians is %zu%s\n",
+                (unsigned long long)with, (unsigned long long)zero, mm, with && mm == (size_t)run.depth_max ? " or more (the last bin, -depth-max)" : "");
+        if (depth) {
+            bool two_mates = false;
+            for (const ReadFile &f : files) two_mates = two_mates || f.paired || f.interleaved;
+            if (!write_depth_report(depth, k, run.depth_reads, run.depth_novalid, run.depth_hist, two_mates)) die("rcorrector: could not write %s\n", depth);
+        }
+    }
     if (report) {  // the contexts' reports, added up
         std::vector<rc_change_report> part(1), sum(1);
         memset(&sum[0], 0, sizeof sum[0]);
