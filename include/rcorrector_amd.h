@@ -348,6 +348,74 @@ int rc_read_keys_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_off
  * not open; RC_STATUS_ARG: dst == src.  No reference counterpart. */
 int rc_dup_census_merge(rc_ctx *dst, rc_ctx *src);
 
+/* ---- recurrent-correction census: one fix made in many reads --------------------------------------------------------------
+ * A sequencing error lands at a random place; a real variant (a minor allele, an editing site, a paralogue's difference) is
+ * rewritten into the dominant spelling in EVERY read that carries it.  The census names the sites where that happened.
+ * A CHANGE is a position p of a read at which the byte of the arena as it arrived differs from the byte as corrected (the
+ * corrected byte is one of upper-case ACGT, as the correction report relies on).  Its WINDOW is the RC_RECUR_FLANK = 14 bytes
+ * on either side of it and the byte itself, the 29 bytes after[p - 14 .. p + 14] of the CORRECTED read -- the stable spelling:
+ * neighbouring fixes have been applied to it too.  A change is CONTEXTED when p >= 14, p + 14 < L (L the read's length) and all
+ * 29 window bytes are upper-case ACGT, exactly as the kernels read letters; every other change is CLIPPED: counted in the
+ * totals, without a key.  The FROM code f is 0..3 when the original byte is upper-case A C G T, else 4 (N, lower case, ...: row
+ * 4 of rc_change_report.subst).  The SITE KEY: W = the window, 2 bits a base (A C G T = 0 1 2 3), first base most significant,
+ * 58 bits; the reverse strand sees the same event as W' = revcomp(W) with f' = 3 - f (4 stays 4); the window's length is odd, so
+ * its centre stays the centre and W != W' always (no base is its own complement): the orientation with the smaller W is
+ * canonical, and key = (W_canon << 3) | f_canon -- 61 bits, one uint64_t, 8 bytes per contexted change.  The new base is the
+ * centre of W_canon (bits 32..31 of the key); rc_recur.h holds this arithmetic for device and host.
+ * The census is the multiset of the keys of all contexted changes of the batches that completed while it was open -- the same
+ * entry points as the duplicate census, each batch once (a packed or resident batch that came back with RC_STATUS_NOSPACE
+ * counts when its resubmission completes); rc_correct_read is no batch of the run and is in none.  A SITE is a distinct key,
+ * its count the changes with that key; changes in the two mates of a pair, or in two copies of a duplicate, count once each.
+ * No census open, those calls launch, copy and allocate nothing for it; open or not, the corrected reads, ret / l / m / h,
+ * rc_summary and rc_table_digest are the same.  The arena as it arrived is the copy the correction report takes (one copy for
+ * the report, the mate-overlap session and this census, whichever are open).
+ *   changes, contexted, clipped   contexted + clipped == changes; changes == changes[0] + changes[1] of an rc_change_report
+ *                                 armed over the same batches
+ *   sites                         distinct keys
+ *   sites_recurrent               sites with two changes or more; changes_at_recurrent: their changes
+ *   recur[c]                      c = 1 .. max_bin: sites with exactly c changes; the last entry: max_bin or more; recur[0] = 0.
+ *                                 The caller's array, max_bin + 1 entries.  sum(recur) == sites
+ *   n_top, top_key, top_count     the sites with min_count changes or more, by count descending, then key ascending -- all of
+ *                                 them, or the first max_sites (exact, not sampled).  The caller's arrays, max_sites entries
+ * begin: RC_STATUS_STATE if open already (needs no table).  get: waits for what is outstanding on the context and its lanes,
+ * sorts a copy of the keys and counts the runs; the keys stay, the census stays open and goes on accumulating, any number of
+ * gets; RC_STATUS_STATE if not open, RC_STATUS_ARG: max_bin < 1 (or above 2^28), min_count < 1, a null pointer (top_key /
+ * top_count may be NULL with max_sites == 0).  end: closes and frees (rc_destroy does too); RC_STATUS_STATE if not open; a batch
+ * in flight across end is in no census, and nothing staged for an ended census reaches the next one.  Where the key buffer
+ * cannot grow, the call that completes the batch returns RC_STATUS_NOSPACE with a message -- a census is never silently short.
+ * A census holds at most 2^32 - 1 keys (its sort indexes them with 32 bits; 32 GiB of keys): the batch that would pass that
+ * returns RC_STATUS_NOSPACE too.  While a census is open every submit and rc_correct_device BLOCK until the batch's kernels have
+ * run: how many keys a batch has is known only then, and the keys that did not fit the first launch's buffer are taken by a
+ * second one while the snapshot is still there (without a census they stay asynchronous); the waits block as they always do.
+ * Threads: as for the duplicate census.  Open, the key kernel reads both arenas in aligned 16-byte pieces: rc_correct_device's
+ * d_seq is read (never written) up to 15 bytes in front of its first and behind its last byte, within the 16-byte granules
+ * those bytes lie in.  No reference counterpart. */
+#define RC_RECUR_FLANK 14
+typedef struct {
+    uint64_t changes, contexted, clipped;
+    uint64_t sites, sites_recurrent, changes_at_recurrent;
+    uint64_t *recur;                /* the caller's, max_bin + 1 entries */
+    uint64_t *top_key, *top_count;  /* the caller's, max_sites entries each */
+    uint32_t n_top;
+} rc_recur_census;
+int rc_recur_census_begin(rc_ctx *ctx);
+int rc_recur_census_get(rc_ctx *ctx, uint32_t max_bin, uint32_t min_count, uint32_t max_sites, rc_recur_census *out);
+int rc_recur_census_end(rc_ctx *ctx);
+/* Appends the keys and totals src has accumulated to dst's (both open; src keeps its own): device to device where the two are
+ * on one device or peers, else through the host.  RC_STATUS_STATE: either one not open; RC_STATUS_ARG: dst == src. */
+int rc_recur_census_merge(rc_ctx *dst, rc_ctx *src);
+/* The site keys of two arenas in HBM as they are: d_before and d_after hold the same n_reads reads (read r the NUL-terminated
+ * string at d_off[r], d_off has n_reads + 1 entries) at the same alignment modulo 16.  The keys of the contexted changes are
+ * appended to d_keys in no particular order, never past d_keys[cap - 1]; d_counts[0 .. 2] (in HBM, zeroed first) = changes,
+ * contexted changes, keys found -- always exact: d_counts[2] > cap says how much room a second call needs.  Asynchronous on the
+ * context's stream (rc_sync() to wait); needs neither a table nor an open census.  Both arenas are read (never written) in
+ * aligned 16-byte pieces: up to 15 bytes in front of their first and behind their last byte, within the 16-byte granules
+ * those bytes lie in; nothing read there reaches a key or a count.  RC_STATUS_ARG: a null pointer (d_keys may be NULL with
+ * cap == 0, the arenas and d_off with n_reads == 0), d_keys or d_counts not 8-byte aligned, arenas of different alignment
+ * modulo 16, an arena of 4 GiB or more.  No reference counterpart. */
+int rc_change_keys_device(rc_ctx *ctx, const uint8_t *d_before, const uint8_t *d_after, const uint32_t *d_off, uint32_t n_reads, uint64_t nbytes,
+                          uint64_t *d_keys, uint64_t cap, uint64_t *d_counts);
+
 /* ---- k-mer trust profile by read position: where along the reads the untrusted k-mers lie, before and after correction ------
  * Window validity, SOLID and WEAK are exactly those of the per-read weak-k-mer profile above (rc_read_weak): at the context's
  * k, against the context's table, at a threshold min_count >= 1.  A read of L bases has nwin = max(0, L - k + 1) windows;

@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "rc_weak_profile_device", "rc_weak_profile_into",
     "rc_read_depth_device", "rc_read_depth_into",
     "rc_dup_census_begin", "rc_dup_census_get", "rc_dup_census_end", "rc_read_keys_device", "rc_dup_census_merge",
+    "rc_recur_census_begin", "rc_recur_census_get", "rc_recur_census_end", "rc_recur_census_merge", "rc_change_keys_device",
     "rc_trust_profile_device", "rc_trust_profile_begin", "rc_trust_profile_get", "rc_trust_profile_end",
     "rc_mate_overlap_device", "rc_mate_overlap_begin", "rc_mate_overlap_get", "rc_mate_overlap_end",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
@@ -95,6 +96,26 @@ class _ChangeReport(C.Structure):
 class _ReadWeak(C.Structure):
     """rc_read_weak: 16 bytes per read"""
     _fields_ = [("weak", C.c_int32), ("bad_prefix", C.c_int32), ("bad_suffix", C.c_int32), ("uncovered", C.c_int32)]
+
+
+class _RecurCensus(C.Structure):
+    """rc_recur_census: six counts, the caller's three arrays, n_top"""
+    _fields_ = [("changes", C.c_uint64), ("contexted", C.c_uint64), ("clipped", C.c_uint64),
+                ("sites", C.c_uint64), ("sites_recurrent", C.c_uint64), ("changes_at_recurrent", C.c_uint64),
+                ("recur", C.c_void_p), ("top_key", C.c_void_p), ("top_count", C.c_void_p), ("n_top", C.c_uint32)]
+
+
+RECUR_FLANK = 14
+
+
+def recur_key_decode(key):
+    """A site key of the recurrence census as (from_letter, to_letter, 29-mer): the canonical window's text, the letter its
+    centre was corrected from ('N': anything but upper-case ACGT) and the centre itself."""
+    key = int(key)
+    f, w = key & 7, key >> 3
+    n = 2 * RECUR_FLANK + 1
+    text = "".join("ACGT"[(w >> (2 * (n - 1 - i))) & 3] for i in range(n))
+    return ("ACGTN"[f] if f <= 4 else "?", text[RECUR_FLANK], text)
 
 
 class _DupCensus(C.Structure):
@@ -232,6 +253,11 @@ def load_library():
     L.rc_dup_census_end.argtypes = [vp]
     L.rc_read_keys_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int, vp]
     L.rc_dup_census_merge.argtypes = [vp, vp]
+    L.rc_recur_census_begin.argtypes = [vp]
+    L.rc_recur_census_get.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_RecurCensus)]
+    L.rc_recur_census_end.argtypes = [vp]
+    L.rc_recur_census_merge.argtypes = [vp, vp]
+    L.rc_change_keys_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, vp, C.c_uint64, vp]
     L.rc_trust_profile_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, vp]
     L.rc_trust_profile_begin.argtypes = [vp, C.c_int32]
     L.rc_trust_profile_get.argtypes = [vp, C.POINTER(_TrustProfile)]
@@ -588,6 +614,46 @@ class Context:
         """rc_dup_census_merge: appends the keys `other` (a Context with an open census, on any device) has accumulated to this
         context's; other keeps its own."""
         self._ck(self._L.rc_dup_census_merge(self._h, other._h))
+
+    # ---- recurrent-correction census: the sites where one fix was made in many reads ----
+    def recur_census_begin(self):
+        """rc_recur_census_begin: from now on every batch that completes on this context (any batch entry point, slot lanes
+        included) leaves a 61-bit site key per contexted change; submits block until their kernels have run while it is open."""
+        self._ck(self._L.rc_recur_census_begin(self._h))
+
+    def recur_census(self, max_bin, min_count=2, max_sites=1000):
+        """rc_recur_census_get: {"changes", "contexted", "clipped", "sites", "sites_recurrent", "changes_at_recurrent", "n_top":
+        int; "recur": uint64 array of max_bin + 1 -- entry c: sites with exactly c changes, the last one max_bin or more;
+        "top_key", "top_count": uint64 arrays of n_top, the sites with min_count changes or more by count descending, then key
+        ascending, at most max_sites; "top_sites": [(count, from_letter, to_letter, 29-mer)] decoded from them}.  The census
+        stays open and cumulative; the keys are kept."""
+        recur = np.zeros(int(max_bin) + 1, dtype=np.uint64)
+        top_key = np.zeros(max(int(max_sites), 1), dtype=np.uint64)
+        top_count = np.zeros(max(int(max_sites), 1), dtype=np.uint64)
+        r = _RecurCensus(0, 0, 0, 0, 0, 0, recur.ctypes.data, top_key.ctypes.data, top_count.ctypes.data, 0)
+        self._ck(self._L.rc_recur_census_get(self._h, int(max_bin), int(min_count), int(max_sites), C.byref(r)))
+        n = int(r.n_top)
+        top_key, top_count = top_key[:n].copy(), top_count[:n].copy()
+        return {"changes": int(r.changes), "contexted": int(r.contexted), "clipped": int(r.clipped), "sites": int(r.sites),
+                "sites_recurrent": int(r.sites_recurrent), "changes_at_recurrent": int(r.changes_at_recurrent), "n_top": n,
+                "recur": recur, "top_key": top_key, "top_count": top_count,
+                "top_sites": [(int(c),) + recur_key_decode(k) for k, c in zip(top_key, top_count)]}
+
+    def recur_census_end(self):
+        """rc_recur_census_end: closes the census and frees the keys."""
+        self._ck(self._L.rc_recur_census_end(self._h))
+
+    def recur_census_merge(self, other):
+        """rc_recur_census_merge: appends the keys and totals `other` (a Context with an open census, on any device) has
+        accumulated to this context's; other keeps its own."""
+        self._ck(self._L.rc_recur_census_merge(self._h, other._h))
+
+    def change_keys_device(self, d_before, d_after, d_off, n_reads, nbytes, d_keys, cap, d_counts):
+        """rc_change_keys_device: the site keys of the contexted changes between two arenas in HBM (same offsets, same alignment
+        modulo 16) appended to d_keys (device memory for cap uint64), never past cap; d_counts: device memory for three uint64
+        -- changes, contexted, keys found (exact even where cap was too small).  Asynchronous: sync() to wait."""
+        self._ck(self._L.rc_change_keys_device(self._h, _ptr(d_before), _ptr(d_after), _ptr(d_off), n_reads, nbytes, _ptr(d_keys), int(cap),
+                                               _ptr(d_counts)))
 
     # ---- k-mer trust profile by read position, before and after correction ----
     def trust_profile_begin(self, min_count=1):

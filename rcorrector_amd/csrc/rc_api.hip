@@ -278,6 +278,7 @@ void rc_destroy(rc_ctx *c)
         if (acc) (void)hipFree(acc);
     if (ctx->trust_acc) (void)hipFree(ctx->trust_acc);  // (the trust profile's counts; its scratch went with the buffers above)
     if (ctx->ovl_acc) (void)hipFree(ctx->ovl_acc);      // (the mate-overlap report's counts)
+    rc_recur_release(ctx);                               // (the recurrence census's keys)
     rc_table_release(ctx);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

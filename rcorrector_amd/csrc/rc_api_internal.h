@@ -159,9 +159,9 @@ void rc_lane_error(rc_ctx *ctx, const rc_ctx *lane);
 // rc_api_table.hip
 // rc_recount_follow: the corrected arena in d_seq appended to the open session, on ctx's own stream; nothing without a session
 int rc_recount_take(rc_ctx *ctx, const void *d_seq, size_t nbytes);
-// rc_api_report.hip -- snapshot: the arena as it is, copied on ctx's stream, where the report is armed or a mate-overlap session
-// open and the batch has pairs (one copy for both; a single-end batch is copied for the report alone); *snap = where (nullptr:
-// none was taken).
+// rc_api_report.hip -- snapshot: the arena as it is, copied on ctx's stream, where the report is armed, a recurrence census is
+// open, or a mate-overlap session is open and the batch has pairs (one copy for all; a single-end batch is not copied for the
+// overlap session alone); *snap = where (nullptr: none was taken).
 // count: the batch against that snapshot, straight into the report (stage == nullptr) or into stage->rep (zeroed first;
 // stage->rep_staged = something was launched).  commit: a staged block into the report.
 int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, bool pairs, const uint8_t **snap);
@@ -182,4 +182,10 @@ int rc_trust_commit(rc_ctx *ctx, rc_trust_staged *st);
 // commit: added to the session, complete on return.
 int rc_overlap_stage(rc_ctx *ctx, const rc_device_batch *b, const uint8_t *snap, rc_overlap_staged *st);
 int rc_overlap_commit(rc_ctx *ctx, rc_overlap_staged *st);
+// rc_api_recur.hip -- stage: behind the last correction kernel, the site keys of the batch's contexted changes, snap
+// (rc_report_snapshot's) against the arena as corrected, into o->recur_keys; WAITS for ctx's stream to learn their number (and
+// launches again into a larger buffer where they did not fit).  commit: appended to the census, complete on return.
+int rc_recur_stage(rc_ctx *ctx, const rc_device_batch *b, const uint8_t *snap, rc_batch_observed *o);
+int rc_recur_commit(rc_ctx *ctx, rc_batch_observed *o);
+void rc_recur_release(rc_ctx *ctx);
 }

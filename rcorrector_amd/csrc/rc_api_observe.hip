@@ -1,6 +1,6 @@
 // rc_api_observe.hip -- where the batch observers meet the correction entry points: the correction report (rc_api_report.hip),
-// the duplicate census (rc_api_dups.hip), the trust profile (rc_api_trust.hip), the mate-overlap report (rc_api_overlap.hip) and
-// the recount session that follows corrected batches (rc_api_table.hip: rc_recount_follow).
+// the duplicate census (rc_api_dups.hip), the trust profile (rc_api_trust.hip), the mate-overlap report (rc_api_overlap.hip), the
+// recurrence census (rc_api_recur.hip) and the recount session that follows corrected batches (rc_api_table.hip: rc_recount_follow).
 //
 // Every batch entry point hands its batch to rc_correct_observed once the bases lie in HBM, and calls rc_batch_completed where
 // the batch is complete and accepted.  Between the two, what the observers took lies in an rc_batch_observed of the slot (or of
@@ -38,6 +38,12 @@ void rc_batch_observed::drop(int parts, bool free_bufs)
         rep_staged = false;
         release(rep);
     }
+    if (parts & RC_OBS_RECUR) {
+        recur_staged = false;
+        recur_n = recur_changes = recur_contexted = 0;
+        release(recur_keys);
+        release(recur_counts);
+    }
 }
 
 extern "C" {
@@ -73,6 +79,7 @@ int rc_correct_observed(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_spl
     if ((rc = rc_dups_stage(ctx, b, 1, o))) return rc;
     if ((rc = rc_trust_stage(ctx, b, 1, &o->trust))) return rc;
     if ((rc = rc_overlap_stage(ctx, b, snap, &o->ovl))) return rc;
+    if ((rc = rc_recur_stage(ctx, b, snap, o))) return rc;
     return rc_report_count(ctx, b, qual_split, qual_base2, qual_bits, snap, stage_report ? o : nullptr);
 }
 
@@ -83,6 +90,7 @@ int rc_batch_completed(rc_ctx *ctx, rc_batch_observed *o, const void *d_seq, siz
     if ((rc = rc_dups_commit(ctx, o))) return rc;
     if ((rc = rc_trust_commit(ctx, &o->trust))) return rc;
     if ((rc = rc_overlap_commit(ctx, &o->ovl))) return rc;
+    if ((rc = rc_recur_commit(ctx, o))) return rc;
     if (!o->rep_staged) return RC_OK;
     o->rep_staged = false;
     return rc_report_commit(ctx, &o->rep);

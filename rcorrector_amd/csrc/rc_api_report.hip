@@ -21,8 +21,8 @@ int rc_report_snapshot(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, bool pa
 {
     *snap_out = nullptr;
     const rc_ctx *home = rc_home(ctx);
-    // (one copy, whichever of the two wants it, or both; the overlap session wants none of a batch without pairs)
-    if ((!home->rep_acc && !(home->ovl_open && pairs)) || !nbytes) return RC_OK;
+    // (one copy, whichever of the three wants it, or all; the overlap session wants none of a batch without pairs)
+    if ((!home->rep_acc && !(home->ovl_open && pairs) && !home->recur_open) || !nbytes) return RC_OK;
     // at the arena's alignment modulo 16: the kernel reads both in aligned 16-byte pieces (up to 15 bytes on either side)
     const size_t lead = (size_t)((uintptr_t)d_seq & 15u);
     if (const int rc = rc_dbuf_reserve(ctx, &ctx->rep_snap, nbytes + 64)) return rc;

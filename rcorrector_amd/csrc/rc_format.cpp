@@ -166,6 +166,27 @@ bool write_dup_census(const char *path, const rc_dup_census &D, uint32_t max_bin
     return fclose(fp) == 0 && ok;
 }
 
+bool write_recur_census(const char *path, const rc_recur_census &R, uint32_t max_bin, uint32_t min_count)
+{
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return false;
+    typedef unsigned long long ull;
+    bool ok = fprintf(fp, "flank\t%d\nmin_count\t%u\nchanges\t%llu\ncontexted\t%llu\nclipped\t%llu\nsites\t%llu\n", RC_RECUR_FLANK, min_count, (ull)R.changes,
+                      (ull)R.contexted, (ull)R.clipped, (ull)R.sites) > 0;
+    for (uint32_t c = 1; c <= max_bin && ok; ++c)
+        if (R.recur[c]) ok = fprintf(fp, "recur\t%u\t%llu\n", c, (ull)R.recur[c]) > 0;
+    const int n = 2 * RC_RECUR_FLANK + 1;
+    for (uint32_t i = 0; i < R.n_top && ok; ++i) {
+        const uint64_t w = R.top_key[i] >> 3;
+        const unsigned f = (unsigned)(R.top_key[i] & 7u);
+        char text[2 * RC_RECUR_FLANK + 2];
+        for (int j = 0; j < n; ++j) text[j] = "ACGT"[(w >> (2 * (n - 1 - j))) & 3u];
+        text[n] = 0;
+        ok = fprintf(fp, "site\t%llu\t%c\t%c\t%s\n", (ull)R.top_count[i], f < 4 ? "ACGT"[f] : 'N', text[RC_RECUR_FLANK], text) > 0;
+    }
+    return fclose(fp) == 0 && ok;
+}
+
 bool write_depth_report(const char *path, int k, const uint64_t reads[2], const uint64_t novalid[2], const std::vector<uint64_t> hist[2], bool two_mates)
 {
     FILE *fp = fopen(path, "wb");

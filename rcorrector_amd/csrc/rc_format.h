@@ -193,6 +193,11 @@ bool write_change_report(const char *path, const rc_change_report &R, bool two_m
 // before <n> / distinct after <n> / copies <c> <distinct before> <distinct after>, a line per c where either is non-zero (the
 // line of c = max_bin: that many copies or more)
 bool write_dup_census(const char *path, const rc_dup_census &D, uint32_t max_bin, const char *unit);
+// the recurrence census (rcorrector_amd.h: rc_recur_census, binned to max_bin, its top list taken at min_count) as tab-separated
+// text: flank 14 / min_count <n> / changes <n> / contexted <n> / clipped <n> / sites <n> / recur <c> <sites>, a line per c
+// that occurs (the line of c = max_bin: that many changes or more) / site <count> <from A|C|G|T|N> <to> <29-mer>, the top
+// sites in the library's order (the canonical window: <to> is its centre)
+bool write_recur_census(const char *path, const rc_recur_census &R, uint32_t max_bin, uint32_t min_count);
 // the trust profile by read position (rcorrector_amd.h: rc_trust_profile) as tab-separated text: k <k> / min_count <n> / reads
 // <mate 1|2> <n> / total <before|after> <mate> <windows> <solid> <weak> <invalid> / pos5 and pos3 <before|after> <mate> <p>
 // <windows> <solid> <weak> <invalid>, a line per position p that some read has a window at; mate 2 only with two_mates.

@@ -92,8 +92,10 @@ struct rc_overlap_staged {
 // What the batch observers (rc_api_observe.hip) keep for one batch in flight, from the submit that staged it to the completion
 // that accepts it: the duplicate census's keys (dup_units before | dup_units after; 0: none were taken) and the census they
 // were taken for, the trust profile's counts, the mate-overlap report's counts, and the correction report's counts where they
-// are staged (rep_staged: this batch left some).  One per slot, and one per context for the entry points that have no slot.
-enum { RC_OBS_DUPS = 1, RC_OBS_TRUST = 2, RC_OBS_REPORT = 4, RC_OBS_OVERLAP = 8, RC_OBS_ALL = 15 };
+// are staged (rep_staged: this batch left some), and the recurrence census's site keys (recur_staged: this batch was looked at;
+// recur_n keys in recur_keys, of recur_changes changes, recur_contexted of them contexted) and the census they were taken for.
+// One per slot, and one per context for the entry points that have no slot.
+enum { RC_OBS_DUPS = 1, RC_OBS_TRUST = 2, RC_OBS_REPORT = 4, RC_OBS_OVERLAP = 8, RC_OBS_RECUR = 16, RC_OBS_ALL = 31 };
 struct rc_batch_observed {
     rc_dbuf dup_keys;
     size_t dup_units = 0;
@@ -102,6 +104,9 @@ struct rc_batch_observed {
     rc_overlap_staged ovl;
     rc_dbuf rep;
     bool rep_staged = false;
+    rc_dbuf recur_keys, recur_counts;
+    bool recur_staged = false;
+    uint64_t recur_n = 0, recur_changes = 0, recur_contexted = 0, recur_gen = 0;
     // nothing staged any more for these observers; free_bufs: their buffers go too
     void drop(int parts, bool free_bufs);
     void reset() { drop(RC_OBS_ALL, false); }
@@ -235,6 +240,14 @@ struct rc_ctx {
     void *ovl_acc = nullptr;
     int32_t ovl_min = 30, ovl_pct = 10;
     uint64_t ovl_gen = 0;
+    // recurrence census (rc_recur_census_begin; kernels in rc_recur.hip).  In the context it was opened on (the batches of its slot
+    // lanes add to it too: rc_home): the site keys of every contexted change seen, 8 bytes each, recur_n of recur_cap, the two
+    // totals, and recur_gen, which counts the begins; the lanes' waits append under obs_mutex.  The arena as it arrived is
+    // rep_snap, the correction report's copy
+    std::atomic<bool> recur_open{false};  // (read by the lanes' submits without the mutex)
+    void *recur_acc = nullptr;
+    size_t recur_n = 0, recur_cap = 0;
+    uint64_t recur_changes = 0, recur_contexted = 0, recur_gen = 0;
     // in the context a batch RUNS in: what the observers staged for the batch of an entry point that has no slot
     // (rc_correct_device, rc_correct_batch_traced)
     rc_batch_observed obs;
@@ -416,6 +429,14 @@ int rc_launch_mate_overlap(rc_ctx *ctx, const uint8_t *d_before, const uint8_t *
 int rc_launch_read_keys(rc_ctx *ctx, hipStream_t st, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int mode,
                         uint64_t *d_keys);
 int rc_dup_census_run(rc_ctx *ctx, const uint64_t *d_keys, size_t n, uint32_t max_bin, uint64_t *copies, uint64_t *distinct);
+
+// rc_recur.hip: the site keys of the contexted changes between two arenas of one alignment modulo 16 that share d_off, appended
+// to d_keys (never past cap) on stream st; d_counts[3] (zeroed first) = changes, contexted changes, keys appended -- the third
+// passes cap where they did not fit.  The census of n keys in HBM (left as they are) into host arrays -- synchronous
+int rc_launch_change_keys(rc_ctx *ctx, hipStream_t st, const uint8_t *d_before, const uint8_t *d_after, const uint32_t *d_off, uint32_t n_reads, size_t nbytes,
+                          uint64_t *d_keys, uint64_t cap, uint64_t *d_counts);
+int rc_recur_census_run(rc_ctx *ctx, const uint64_t *d_keys, size_t n, uint32_t max_bin, uint32_t min_count, uint32_t max_sites, uint64_t *recur,
+                        uint64_t *sites, uint64_t *sites_recurrent, uint64_t *changes_at_recurrent, uint64_t *top_key, uint64_t *top_count, uint32_t *n_top);
 
 // rc_transport.hip: the packed boundary (include/rcorrector_amd.h: rc_packed_batch)
 int rc_launch_unpack(rc_ctx *ctx, const uint32_t *d_packed, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, const uint32_t *d_exc_pos,

@@ -27,6 +27,8 @@
 // substitutions by position, letters, quality class, mate and read, counted on the GPU as the batches complete.
 // -weak-ends tags every record with the reference's dormant bad_prefix= / bad_suffix= fields (Reads.h:396-412), filled from the
 // weak-k-mer profile of the corrected reads (rcorrector_amd.h: rc_read_weak; -weak-min: the count below which a k-mer is weak).
+// -recurrent FILE writes the recurrent-correction census (rcorrector_amd.h: rc_recur_census; rc_format.h: write_recur_census): the
+// sites -- 29 corrected bases around a change, and what it was corrected from -- at which the run made one fix in many reads.
 // -dups FILE writes the duplicate census (rcorrector_amd.h: rc_dup_census; rc_format.h: write_dup_census): how many reads or
 // pairs are exact copies of one another, as uploaded and as corrected, from 128-bit keys taken on the GPU as the batches complete.
 // -trust-by-pos FILE writes the k-mer trust profile by read position (rcorrector_amd.h: rc_trust_profile; rc_format.h:
@@ -101,6 +103,16 @@ static void print_help()
             "\t\tin GPU memory until the end of the run, at most 2^32 - 1 units; with -gpus above 1 the GPUs' keys are merged on the\n"
             "\t\tfirst; the input is all single-end or all paired (-p / -i), not a mix; not with -verbose\n"
             "\t-dups-max INT: with -dups, units with this many copies or more are counted in the last line (default: 10000)\n"
+            "\t-recurrent STRING: also write the recurrent-correction census, tab-separated text: the changed bases, those with 14\n"
+            "\t\tupper-case ACGT bases of the corrected read on either side (contexted) and the others (clipped), the distinct sites -- the\n"
+            "\t\t29 corrected bases around a change and the letter it was corrected from, either strand read as one -- for every number\n"
+            "\t\tof changes c the sites corrected c times, and the sites corrected most often: count, from, to, 29-mer; a site fixed in\n"
+            "\t\tmany reads is a candidate for a real variant that was corrected away; one more line on stderr; the keys (8 bytes per\n"
+            "\t\tcontexted change) stay in GPU memory until the end of the run, at most 2^32 - 1; with -gpus above 1 the GPUs' keys\n"
+            "\t\tare merged on the first; not with -verbose\n"
+            "\t-recurrent-min INT: with -recurrent, the fewest changes of a listed site (default: 5)\n"
+            "\t-recurrent-top INT: with -recurrent, the most sites listed (default: 1000)\n"
+            "\t-recurrent-max INT: with -recurrent, sites with this many changes or more are counted in the last recur line (default: 10000)\n"
             "\t-trust-by-pos STRING: also write the k-mer trust profile by read position, tab-separated text: for every k-mer window\n"
             "\t\tposition counted from the 5' end (pos5) and from the 3' end (pos3, 0 = the last window), per mate, before and after\n"
             "\t\tcorrection: the reads that have a window there and those whose window is solid (in the table at least -weak-min\n"
@@ -126,7 +138,8 @@ int main(int argc, char **argv)
     int max_fix_per_k = 4, i;
     double wk = 0.95;
     const char *dump = nullptr, *write_dump = nullptr, *histo = nullptr, *histo_after = nullptr, *report = nullptr, *dups = nullptr, *trust = nullptr;
-    const char *overlap = nullptr, *depth = nullptr;
+    const char *overlap = nullptr, *depth = nullptr, *recurrent = nullptr;
+    long recur_min = 5, recur_top = 1000, recur_max = 10000;
     long depth_max = 10000;
     int overlap_min = 30, overlap_mm = 10;
     long dups_max = 10000;
@@ -191,6 +204,14 @@ int main(int argc, char **argv)
             dups = argv[++i];
         else if (!strcmp("-dups-max", argv[i]))
             dups_max = atol(argv[++i]);
+        else if (!strcmp("-recurrent", argv[i]))
+            recurrent = argv[++i];
+        else if (!strcmp("-recurrent-min", argv[i]))
+            recur_min = atol(argv[++i]);
+        else if (!strcmp("-recurrent-top", argv[i]))
+            recur_top = atol(argv[++i]);
+        else if (!strcmp("-recurrent-max", argv[i]))
+            recur_max = atol(argv[++i]);
         else if (!strcmp("-trust-by-pos", argv[i]))
             trust = argv[++i];
         else if (!strcmp("-overlap", argv[i]))
@@ -226,6 +247,10 @@ int main(int argc, char **argv)
     run.depth_on = run.depth_tags || depth;
     run.depth_max = (uint32_t)depth_max;
     if (dups && verbose) die("rcorrector: usage: -dups cannot be combined with -verbose (small batches through the transcript's entry point: run the census without it)\n");
+    if (recurrent && verbose) die("rcorrector: usage: -recurrent cannot be combined with -verbose (small batches through the transcript's entry point: run the census without it)\n");
+    if (recurrent && (recur_max < 1 || recur_max > (1l << 28))) die("rcorrector: usage: -recurrent-max must be 1..%ld\n", 1l << 28);
+    if (recurrent && (recur_min < 1 || recur_min > recur_max)) die("rcorrector: usage: -recurrent-min must be 1..-recurrent-max\n");
+    if (recurrent && (recur_top < 0 || recur_top > (1l << 28))) die("rcorrector: usage: -recurrent-top must be 0..%ld\n", 1l << 28);
     if (trust && verbose) die("rcorrector: usage: -trust-by-pos cannot be combined with -verbose (small batches through the transcript's entry point: run the profile without it)\n");
     if (overlap && verbose) die("rcorrector: usage: -overlap cannot be combined with -verbose (small batches through the transcript's entry point: run the report without it)\n");
     if (overlap && (overlap_min < 1 || overlap_min > 1023)) die("rcorrector: usage: -overlap-min must be 1..1023\n");
@@ -581,6 +606,11 @@ int main(int argc, char **argv)
         for (int c = 0; c < nctx; ++c)
             if (rc_dup_census_begin(ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
 
+    // -recurrent: every context keeps the site keys of the batches that complete on it, whatever the transport
+    if (recurrent)
+        for (int c = 0; c < nctx; ++c)
+            if (rc_recur_census_begin(ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[c]));
+
     // -trust-by-pos: every context counts the batches that complete on it, whatever the transport
     if (trust)
         for (int c = 0; c < nctx; ++c)
@@ -674,6 +704,28 @@ int main(int argc, char **argv)
         fprintf(stderr, "Duplicates: %llu %s, %llu distinct before correction (duplicate fraction %.4f), %llu after (%.4f)\n", (unsigned long long)dc.units, unit,
                 (unsigned long long)dc.distinct_before, dc.units ? 1.0 - (double)dc.distinct_before / u : 0.0, (unsigned long long)dc.distinct_after,
                 dc.units ? 1.0 - (double)dc.distinct_after / u : 0.0);
+    }
+    if (recurrent) {  // the contexts' keys, merged into the first
+        const double tr0 = now_s();
+        for (int c = 1; c < nctx; ++c)
+            if (rc_recur_census_merge(ctx[0], ctx[c])) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+        std::vector<uint64_t> bins((size_t)recur_max + 1), tk((size_t)recur_top + 1), tc((size_t)recur_top + 1);
+        rc_recur_census rcs;
+        rcs.recur = bins.data();
+        rcs.top_key = tk.data();
+        rcs.top_count = tc.data();
+        if (rc_recur_census_get(ctx[0], (uint32_t)recur_max, (uint32_t)recur_min, (uint32_t)recur_top, &rcs)) die("rcorrector: %s\n", rc_last_error(ctx[0]));
+        if (!write_recur_census(recurrent, rcs, (uint32_t)recur_max, (uint32_t)recur_min)) die("rcorrector: could not write %s\n", recurrent);
+        if (g_timing) fprintf(stderr, "[rc timing] -recurrent: merge, sort and census %.2f s\n", now_s() - tr0);
+        // (the bins below -recurrent-min are exact, -recurrent-min <= -recurrent-max: what is not in them repeats that often)
+        uint64_t few_sites = 0, few_changes = 0;
+        for (long c = 1; c < recur_min; ++c) {
+            few_sites += bins[(size_t)c];
+            few_changes += bins[(size_t)c] * (uint64_t)c;
+        }
+        fprintf(stderr, "Recurrent corrections: %llu contexted changes at %llu sites; %llu changes at %llu sites corrected at least %ld times\n",
+                (unsigned long long)rcs.contexted, (unsigned long long)rcs.sites, (unsigned long long)(rcs.contexted - few_changes),
+                (unsigned long long)(rcs.sites - few_sites), recur_min);
     }
     if (trust) {  // the contexts' counts, added up
         std::vector<rc_trust_profile> tp(2);
