@@ -128,6 +128,97 @@ bool pack_quality_bits_from_text(const QualView &V, char bad_q, size_t lo, size_
     return ok;
 }
 
+void pack_quality_bits_from_arenas(const QualView &V, char bad_q, size_t lo, size_t hi, uint8_t *bits)
+{
+    const char *q1 = V.A[0]->qual.data(), *q2 = V.A[1]->qual.data();
+    for (size_t p8 = lo; p8 < hi; p8 += 8) {
+        unsigned v = 0;
+        for (size_t q = p8; q < std::min(p8 + 8, hi); ++q) {
+            const signed char c = (signed char)(q < V.bytes1 ? q1[q] : q2[q - V.bytes1]);
+            v |= (unsigned)(c > (signed char)bad_q) << (q - p8);
+        }
+        bits[p8 >> 3] = (uint8_t)v;
+    }
+}
+
+// One bit per quality cannot say "this read has no quality string" (qual[0] == 0: an empty quality line in a FASTQ file;
+// ErrorCorrection.cpp:1316 asks): such a batch takes the bytes
+bool has_empty_quality_read(const Job &J)
+{
+    if (!J.fastq) return false;
+    for (int sd = 0; sd < (J.mode == 1 ? 2 : 1); ++sd) {
+        const Arena &A = sd ? J.b : J.a;
+        for (size_t r = 0; r < A.n(); ++r)
+            if (A.off[r + 1] - A.off[r] > 1 && A.qual.data()[A.off[r]] == 0) return true;
+    }
+    return false;
+}
+
+void combined_offsets(const Job &J, uint32_t *off)
+{
+    const size_t n = J.a.n();
+    memcpy(off, J.a.off.data(), (n + 1) * 4);
+    if (J.mode == 1)
+        for (size_t r = 0; r <= n; ++r) off[n + r] = J.a.off[n] + J.b.off[r];
+}
+
+size_t pack_bases_of(Job &J, size_t nbytes, size_t bytes1)
+{
+    const size_t n_words = (nbytes + 15) / 16;
+    J.pk_bases.need(n_words * 4 + 64);
+    uint32_t *bases = (uint32_t *)J.pk_bases.data();
+    const size_t P = std::max<size_t>(1, std::min<size_t>((size_t)g_threads, n_words / 4096 + 1));
+    std::vector<std::vector<uint32_t>> ep(P);  // the exceptions of each piece
+    std::vector<std::vector<uint8_t>> ec(P);
+    g_pool.run(P, [&](size_t t) {
+        const size_t lo = (n_words * t / P) * 16, hi = std::min((n_words * (t + 1) / P) * 16, nbytes);
+        for (int pass = 0; pass < 2; ++pass) {  // (first pass counts the exceptions, second stores them)
+            uint32_t *pp = pass ? ep[t].data() : nullptr;
+            uint8_t *pc = pass ? ec[t].data() : nullptr;
+            const size_t room = pass ? ep[t].size() : 0;
+            size_t got = 0, cnt = 0;
+            if (lo < bytes1) cnt += (got = rc_pack_bases(J.a.seq.data(), lo, std::min(hi, bytes1), bases, pp, pc, room));
+            if (hi > bytes1) {  // arena 2's share, behind what arena 1's left in the lists
+                const size_t used = std::min(got, room);
+                cnt += rc_pack_bases(J.b.seq.data() - bytes1, std::max(lo, bytes1), hi, bases, pp ? pp + used : nullptr, pc ? pc + used : nullptr, room - used);
+            }
+            if (pass == 0) {
+                if (cnt == 0) break;
+                ep[t].resize(cnt);
+                ec[t].resize(cnt);
+            }
+        }
+    });
+    size_t n_exc = 0;
+    for (size_t t = 0; t < P; ++t) n_exc += ep[t].size();
+    J.pk_exc_pos.need(n_exc * 4 + 64);
+    J.pk_exc_chr.need(n_exc + 64);
+    size_t at = 0;
+    for (size_t t = 0; t < P; ++t) {
+        if (ep[t].empty()) continue;
+        memcpy(J.pk_exc_pos.data() + at * 4, ep[t].data(), ep[t].size() * 4);
+        memcpy(J.pk_exc_chr.data() + at, ec[t].data(), ec[t].size());
+        at += ep[t].size();
+    }
+    return n_exc;
+}
+
+void apply_fixes(Job &J, size_t bytes1, const uint32_t *fix_pos, const uint8_t *fix_chr, size_t n_fix)
+{
+    const size_t F = std::max<size_t>(1, std::min<size_t>((size_t)g_threads, n_fix / 16384 + 1));
+    g_pool.run(F, [&](size_t t) {
+        const size_t lo = n_fix * t / F, hi = n_fix * (t + 1) / F;
+        if (J.a.seq_in_text) {
+            apply_fixes_to_text(J.a, J.mode == 1 ? &J.b : nullptr, bytes1, fix_pos, fix_chr, lo, hi);
+            return;
+        }
+        for (size_t q = lo; q < hi; ++q) {
+            const size_t pos = fix_pos[q];
+            (pos < bytes1 ? J.a.seq.data()[pos] : J.b.seq.data()[pos - bytes1]) = (char)fix_chr[q];
+        }
+    });
+}
+
 void apply_fixes_to_text(Arena &A1, Arena *A2, size_t bytes1, const uint32_t *fix_pos, const uint8_t *fix_chr, size_t lo, size_t hi)
 {
     for (size_t q = lo; q < hi; ++q) {

@@ -1,5 +1,5 @@
 // rc_format.h -- a batch between the reader and the writer of the `rcorrector` CLI: the SoA arenas of the C ABI packed from
-// the text, quality bits and fixes of the one-pass path, and the output records.
+// the text, the host steps of the resident and packed transports (offsets, quality bits, 2-bit bases, fixes), and the output records.
 //   record       Reads.h:224-266,360-421    4 lines in; "<id> l:%d m:%d h:%d[ cor| unfixable_error]" out
 //   -weak-ends   Reads.h:396-412            " bad_prefix=%d" / " bad_suffix=%d" behind " cor": the reference's dormant tags
 //   -depth-tags  (no reference counterpart) " kdepth=Q1:MED:Q3" behind those: the quartiles of the read's k-mer counts
@@ -89,9 +89,39 @@ struct QualView {
     size_t nbytes;
 };
 bool pack_quality_bits_from_text(const QualView &V, char bad_q, size_t lo, size_t hi, uint8_t *bits);
+// The same bits from the byte arenas pack_arena made (a packed batch): same view, same ranges.  The arenas cannot say "no
+// quality string" in one bit either; the caller has asked has_empty_quality_read() before.
+void pack_quality_bits_from_arenas(const QualView &V, char bad_q, size_t lo, size_t hi, uint8_t *bits);
+// The ranges both are called with: piece(lo, hi) over up to g_threads pieces of [0, nbytes) side by side on g_pool, one per
+// `grain` bytes, cut at multiples of 8 so that no two pieces share a byte of the bit array.  False if a piece returned false.
+template <class F>
+inline bool for_quality_pieces(size_t nbytes, F piece, size_t grain = 65536)
+{
+    const size_t Q = std::max<size_t>(1, std::min<size_t>((size_t)g_threads, nbytes / grain + 1));
+    std::vector<char> ok(Q, 1);
+    g_pool.run(Q, [&](size_t t) {
+        const size_t lo = (nbytes * t / Q) & ~(size_t)7, hi = t + 1 == Q ? nbytes : ((nbytes * (t + 1) / Q) & ~(size_t)7);
+        if (lo < hi) ok[t] = piece(lo, hi) ? 1 : 0;
+    });
+    return std::find(ok.begin(), ok.end(), 0) == ok.end();
+}
+// a FASTQ batch (its byte arenas) with a read that has bases and no first quality character: see above
+bool has_empty_quality_read(const Job &J);
+
+// one offset array over both arenas, n + 1 or 2 n + 1 entries: arena 2's offsets follow arena 1's, moved up by its size
+void combined_offsets(const Job &J, uint32_t *off);
+
+// The bases of a packed batch (nbytes of byte arena, the first bytes1 of them arena 1's) into J.pk_bases, and the letters
+// outside ACGT into J.pk_exc_pos / J.pk_exc_chr in ascending order; returns how many of those there are.  rc_pack_bases over
+// up to g_threads 16-byte-aligned pieces of the combined arena side by side, one per 4096 words, each counting its exceptions
+// before it stores them; the piece that holds the seam between the arenas packs either side of it in turn.
+size_t pack_bases_of(Job &J, size_t nbytes, size_t bytes1);
 
 // the substitutions of a resident batch, applied to the sequence lines of the text
 void apply_fixes_to_text(Arena &A1, Arena *A2, size_t bytes1, const uint32_t *fix_pos, const uint8_t *fix_chr, size_t lo, size_t hi);
+// a fix list (positions in the combined arena, distinct: any number of threads) applied where the batch's sequences are: the
+// text's sequence lines (seq_in_text) or the byte arenas
+void apply_fixes(Job &J, size_t bytes1, const uint32_t *fix_pos, const uint8_t *fix_chr, size_t n_fix);
 
 static inline char *put_int(char *p, int v)
 {
