@@ -744,7 +744,12 @@ int rc_strong_threshold_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t
  *       corrected in place, *ret = the return value; pair_strong_threshold = min of the two mates' strong thresholds, or
  *       -1 for a read without a mate (:96-106); qual == NULL stands for a FASTA record (qual[0] == 0, Reads.h:241);
  *       counted by rc_summary like any batch;
- *   rc_kmer_info_read         = GetKmerInformation(seq, kmerLength, kmers, l, m, h), :1567-1602, of the read as given. */
+ *   rc_kmer_info_read         = GetKmerInformation(seq, kmerLength, kmers, l, m, h), :1567-1602, of the read as given.
+ * Rules of all three (tests/test_per_read.py):
+ *   - qual is a C string of its own length: one shorter than the read counts as padded with NULs (the bases behind it have
+ *     quality 0, an empty one is a FASTA record like NULL), one longer is read up to the read's length;
+ *   - a read of more than 1023 bases is RC_ERR_ARG (utils.h:7: MAX_READ_LENGTH 1024 with the NUL); seq is left as it was;
+ *   - while rc_set_quality_bits is on, the calls are RC_ERR_STATE: they take quality bytes. */
 int rc_strong_threshold_read(rc_ctx *ctx, const char *seq, int32_t *strong);
 int rc_correct_read(rc_ctx *ctx, char *seq, const char *qual, int32_t pair_strong_threshold, int32_t *ret);
 int rc_kmer_info_read(rc_ctx *ctx, const char *seq, int32_t *l, int32_t *m, int32_t *h);

@@ -63,6 +63,11 @@ def lib():
         L.rco_kmer_counts.argtypes = [C.POINTER(Params), C.c_void_p, C.c_char_p, C.c_void_p]
         L.rco_strong_trusted_threshold.restype = C.c_int
         L.rco_strong_trusted_threshold.argtypes = [C.POINTER(Params), C.c_void_p, C.c_char_p]
+        L.rco_error_correction.restype = C.c_int
+        L.rco_error_correction.argtypes = [C.POINTER(Params), C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
+        L.rco_kmer_information.restype = None
+        L.rco_kmer_information.argtypes = [C.POINTER(Params), C.c_void_p, C.c_char_p,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rco_get_bound_int.restype = C.c_int
         L.rco_get_bound_int.argtypes = [C.POINTER(Params), C.c_int]
         L.rco_get_bound.restype = C.c_double
@@ -183,3 +188,30 @@ def kmer_counts(params, table, seq_bytes):
     buf = np.zeros(1024, dtype=np.int32)
     n = lib().rco_kmer_counts(C.byref(params), table.h, seq_bytes, buf.ctypes.data)
     return buf[:n].copy()
+
+
+# ---- the reference's three per-read functions (ErrorCorrection.h:26-28), one read (bytes, no NUL inside) per call ----
+
+def strong_threshold(params, table, seq):
+    """GetStrongTrustedThreshold of one read."""
+    return lib().rco_strong_trusted_threshold(C.byref(params), table.h, bytes(seq))
+
+
+def error_correction(params, table, seq, qual, pair_t=-1):
+    """ErrorCorrection of one read -> (return value, corrected bytes).  seq is copied into a buffer of the call's own; qual
+    (None: none) goes in a buffer padded with NULs to the read's length, so a quality string shorter than the read -- it ends at
+    its first NUL, as a C string does -- is defined behaviour here: the bases behind it have quality 0, and a string that is empty
+    is the FASTA marker qual[0] == 0 (ErrorCorrection.cpp:1295)."""
+    seq = bytes(seq)
+    buf = C.create_string_buffer(seq)
+    q = bytes(qual or b"").split(b"\0")[0][:len(seq)]
+    qbuf = C.create_string_buffer(q, len(seq) + 1)
+    ret = lib().rco_error_correction(C.byref(params), table.h, None, buf, qbuf, int(pair_t))
+    return ret, buf.value
+
+
+def kmer_information(params, table, seq):
+    """GetKmerInformation of one read -> (l, m, h)."""
+    l, m, h = C.c_int(0), C.c_int(0), C.c_int(0)
+    lib().rco_kmer_information(C.byref(params), table.h, bytes(seq), C.byref(l), C.byref(m), C.byref(h))
+    return l.value, m.value, h.value

@@ -260,4 +260,53 @@ void hostsim_correct_batch(const rco_params *p, const rco_table *t, rco_batch *b
         st->reads = (long)total;
     }
 }
+
+// What one k_correct wave does for rc_correct_read (rc_api_batch.hip): no threshold kernel ran, so the front end runs inside
+// (the fused branch of rc_correct_kernel.h: rc_front_end leaves the poly-A flags behind, nobody sets them from outside) and
+// the pair's threshold is the caller's argument.  seq (NUL-terminated) is corrected in place; qual is a C string that may be
+// shorter than the read or NULL, the bases behind it have quality 0 (one_read_upload).
+void hostsim_correct_read(const rco_params *p, const rco_table *t, char *seq, const char *qual, int pair_t, int32_t *ret,
+                          int32_t *l, int32_t *m, int32_t *h)
+{
+    rc_run_params P;
+    P.k = p->k;
+    P.max_fix_per_k = p->max_fix_per_k;
+    P.error_rate = p->error_rate;
+    P.bad_qual = (int)(signed char)p->bad_qual;
+    static std::vector<uint32_t> bsteps;  // (one table per error rate, as a context has: the callers sweep thousands of reads)
+    static double bsteps_rate;
+    if (bsteps.empty() || memcmp(&bsteps_rate, &P.error_rate, sizeof bsteps_rate) != 0) {
+        bsteps.resize(RC_BOUND_STEPS);
+        rc_bound_steps_build(P.error_rate, bsteps.data());
+        bsteps_rate = P.error_rate;
+    }
+    for (int v = 0; v < RC_BS_INLINE; ++v) P.bs[v] = bsteps[v];
+    P.bs_ext = bsteps.data();
+    P.bound_small = nullptr;
+    P.flags = 0;
+    Buffers B(RC_MAX_READ_LENGTH + 64);
+    HostWave w;
+    w.tab = t;
+    w.k = p->k;
+    load_read(B, w, p, t, seq);
+    const size_t qn = qual ? strnlen(qual, (size_t)B.S.len) : 0;
+    for (int i = 0; i < B.S.len; ++i) B.S.qual[i] = (size_t)i < qn ? (signed char)qual[i] : (signed char)0;
+    int info0;
+    const int strong0 = rc_front_end(w, B.S, P, &info0);
+    const int r = rc_correct_read(w, B.S, P, pair_t, strong0, info0);
+    if (r > 0) {
+        for (int i = 0; i < B.S.len; ++i)
+            if (B.S.best[i] != -1) {
+                seq[i] = "ACGT"[B.S.best[i]];
+                B.S.base[i] = (unsigned char)B.S.best[i];
+            }
+        rc_pack_read(w, B.S);
+    }
+    int ll, mm, hh;
+    rc_kmer_info(w, B.S, P, r, &ll, &mm, &hh);
+    *ret = r;
+    *l = ll;
+    *m = mm;
+    *h = hh;
+}
 }
