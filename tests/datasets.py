@@ -424,6 +424,8 @@ def make(name):
     their threshold byte (badq)."""
     if name.startswith("qv_"):
         return qv_make(name)
+    if name.startswith("huge_"):
+        return huge_make(name)
     if name.startswith("polya_k"):
         k = int(name[len("polya_k"):])
         s1, q1 = polya_boundary_reads(k)
@@ -493,6 +495,87 @@ def k_sweep(k, mode, pad_to=0):
     def rows(a):
         return None if a is None else [r.tobytes() for r in a]
     return dict(k=k, mfk=4, rate=0.01, mode=mode, keys=keys, counts=cnt, seqs1=rows(s1), quals1=rows(q1), seqs2=rows(s2), quals2=rows(q2))
+
+
+# ---- huge_*: the k sweep's reads over tables whose counts do not fit a PACKED slot's count field ----
+# A PACKED slot keeps a count in 27 - ext bits; the all-ones value is the mark of a count kept in full in the table's prefix
+# (rc_common.h: RC_PACKED_OVF_MAX), so with limit = 2^(27 - ext) the counts up to limit - 2 are inline and those from limit - 1
+# (the mark's own value) on overflow.  The second cliff is RC_BOUND_STEPS = 65536: a threshold t >= 65536 is beyond the table
+# of GetBound's steps (rc_bs_lookup gives "not known").  Regime A keeps every threshold below it, regime B (rate 0.01) does not.
+RC_PACKED_OVF_MAX = 4000
+RC_BOUND_STEPS = 65536
+INT_MAX = (1 << 31) - 1
+# member -> k, mode, entries the table is padded to, regime A's rate; `fallback`: more than RC_PACKED_OVF_MAX counts overflow
+HUGE = {
+    "huge_k23_ext0": dict(k=23, mode=0, pad_to=30_000, rate_a=1e-5),
+    "huge_k27_ext8": dict(k=27, mode=1, pad_to=26_400, rate_a=1e-3),
+    "huge_k23_small": dict(k=23, mode=0, pad_to=0, rate_a=1e-5),
+    "huge_k31_wide": dict(k=31, mode=2, pad_to=0, rate_a=1e-5),
+    "huge_k23_fallback": dict(k=23, mode=0, pad_to=30_000, rate_a=1e-5, fallback=True),
+}
+HUGE_NAMES = ["%s/%s" % (m, r) for m in HUGE for r in "AB"]
+HUGE_FALLBACK_PADS = 2200
+
+
+def packed_rule(k, n, load=0.4):
+    """(ext, home buckets) of the PACKED attempt the build makes for n entries (rc_table.hip:
+    rc_build_table_from_device_pairs): n / (4 slots * load) + 1 home buckets, at least 64, and the smallest ext with
+    buckets << ext >= 2^(2k-32).  The attempt is made while ext <= 8 and stands while at most RC_PACKED_OVF_MAX counts
+    overflow; otherwise the table is WIDE."""
+    b = max(64, int(n / (4 * load)) + 1)
+    ext = 0
+    while 2 * k > 32 and (b << ext) < (1 << (2 * k - 32)):
+        ext += 1
+    return ext, b
+
+
+def huge_overflowing(counts, ext):
+    """how many counts a PACKED table with `ext` extension bits keeps in its prefix"""
+    return int((np.asarray(counts, dtype=np.int64) >= (1 << (27 - ext)) - 1).sum())
+
+
+_HUGE = {}
+
+
+def huge_make(name):
+    """huge_<member>/<regime>: k_sweep's reads (600 reads or pairs of 100 bases), every count of the reads' own k-mers multiplied
+    by S = min(limit // 8, INT_MAX // largest count) -- the k-mers seen 8 times or more overflow, the error k-mers (2..3) stay
+    inline -- the padding left alone, and four true k-mers (seen 8 times or more) pinned to limit - 2 (the largest inline
+    count), limit - 1 (the mark's own value), limit and, without extension bits, INT_MAX.  limit = 2^(27 - ext) of the PACKED
+    table the build makes for the member's size; huge_k31_wide would need more than 8 extension bits and is WIDE, and takes the
+    limit of a count field without any (it is the member that has INT_MAX in a WIDE slot).  The fall-back member: S = limit // 4,
+    so that the counts of 4 or more overflow too, and HUGE_FALLBACK_PADS padding k-mers beyond the limit: more counts than the
+    prefix holds, the build has to fall back to WIDE by itself.  The dict also carries ext, limit, scale, the pinned
+    (code, count) pairs and the unscaled counts (base_counts)."""
+    member, regime = name.split("/")
+    if member not in _HUGE:
+        c = HUGE[member]
+        k = c["k"]
+        d = k_sweep(k, 1 if c["mode"] else 0, c["pad_to"])
+        own = len(k_sweep(k, 1 if c["mode"] else 0)["keys"])   # (the padding comes behind the reads' own k-mers)
+        base = np.asarray(d["counts"], dtype=np.int64)
+        ext, _ = packed_rule(k, len(base))
+        limit = 1 << (27 - (ext if ext <= 8 else 0))
+        top = int(base[:own].max())
+        scale = min(limit // (4 if c.get("fallback") else 8), INT_MAX // top)
+        cnt = base.copy()
+        cnt[:own] *= scale
+        pins = [limit - 2, limit - 1, limit] + ([INT_MAX] if ext == 0 or ext > 8 else [])
+        deep = np.nonzero(base[:own] >= 8)[0]
+        at = deep[np.linspace(0, len(deep) - 1, len(pins) + 2).astype(int)[1:-1]]
+        cnt[at] = pins
+        if c.get("fallback"):
+            cnt[own:own + HUGE_FALLBACK_PADS] = limit + np.arange(HUGE_FALLBACK_PADS)
+        assert cnt.max() <= INT_MAX and len(set(at.tolist())) == len(pins)
+        if c["mode"] == 2:
+            d = dict(d, mode=2, seqs1=[x for p in zip(d["seqs1"], d["seqs2"]) for x in p],
+                     quals1=[x for p in zip(d["quals1"], d["quals2"]) for x in p], seqs2=None, quals2=None)
+        cnt.setflags(write=False)
+        base.setflags(write=False)
+        _HUGE[member] = dict(d, counts=cnt, base_counts=base, own=own, ext=ext, limit=limit, scale=scale,
+                             pinned=[(int(d["keys"][i]), int(v)) for i, v in zip(at, pins)], rate_a=c["rate_a"])
+    d = _HUGE[member]
+    return dict(d, rate=d["rate_a"] if regime == "A" else 0.01, regime=regime)
 
 
 def run_oracle(po, d, threads=4, fn=None):

@@ -151,7 +151,17 @@ def main():
             differ += sum(a[i:i + 2] != b[i:i + 2] for i in range(0, 4 * 150, 4))   # (header with l / m / h and verdict, bases)
     print("fx_qual_veto: %d of 300 records depend on their qualities" % differ)
     assert differ >= 30, differ
-    # --- FASTA input (Reads.h:108-162).  The reference's -t 1 loop hands ErrorCorrection a NULL quality
+    # --- counts beyond the count field of a PACKED table slot (tests/datasets.py: huge_k23_small): the first 300 reads with the
+    # whole dump -- 2 388 entries, a PACKED table with four extension bits (limit 2^23), counts of 2 M .. 51 M, 1 893 of them at
+    # or beyond the mark.  (huge_k27_ext8 needs a dump of 26 400 entries for its eight extension bits, twice the largest
+    # fixture here; the GPU tests run it through the transports the command line uses.)
+    d = os.path.join(HERE, "fx_hugecount")
+    os.makedirs(d, exist_ok=True)
+    ds = datasets.make("huge_k23_small/B")
+    run_ref(d, datasets.write_cli_case(ds, d, units=300))
+    assert ds["ext"] == 4 and datasets.huge_overflowing(ds["counts"], 4) >= 1000
+    assert b"Stored 2388 kmers" in open(os.path.join(d, "ref", "stderr.txt"), "rb").read()
+    # --- FASTA input (Reads.h:108-162). The reference's -t 1 loop hands ErrorCorrection a NULL quality
     # pointer for FASTA records and crashes in the pairwise veto (main.cpp:376-379, ErrorCorrection.cpp:1316);
     # its batch path (-t > 1) passes a buffer whose first byte is 0 (Reads.h:241) and works: that is the
     # behaviour pinned here.  No -verbose transcript (threads interleave their prints).  The directory

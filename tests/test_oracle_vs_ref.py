@@ -70,6 +70,29 @@ def test_oracle_dump_loader_equals_reference_on_quirky_dumps(oracle, seed, tmp_p
     assert res[0][0] == 0 and res[0] == res[1]
 
 
+@pytest.mark.parametrize("name", ["huge_k23_ext0/B", "huge_k27_ext8/B"])
+def test_oracle_cli_equals_reference_on_counts_up_to_int_max(oracle, name, tmp_path):
+    """The huge_ data sets (tests/datasets.py) as files: counts of 10^5 .. 2^31 - 1 in the dump, so GetBound's (int)
+    conversions, the thresholds beyond 65536 and the ERROR_RATE sample (main.cpp:329-345, sums of such counts) are the
+    reference's own in the oracle that the GPU tests of these sets lean on."""
+    import datasets
+    if not os.path.exists(oracle.REF_BIN):
+        pytest.skip("oracle/_ref not built (needs /root/reference)")
+    d = str(tmp_path)
+    ds = datasets.make(name)
+    assert max(c for _, c in ds["pinned"]) == (datasets.INT_MAX if ds["ext"] == 0 else ds["limit"])
+    args = datasets.write_cli_case(ds, d)
+    res = []
+    for tag, binary, more in (("ref", oracle.REF_BIN, []), ("ora", oracle.CLI_BIN, ["-t", "2"])):
+        od = os.path.join(d, tag)
+        os.makedirs(od)
+        p = subprocess.run([binary] + args + ["-od", od] + more, cwd=d, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        res.append((p.returncode, p.stderr, {f: open(os.path.join(od, f), "rb").read() for f in sorted(os.listdir(od))}))
+    assert res[0][0] == 0 and res[0][2] and res[0] == res[1]
+    heads = b"".join(res[0][2].values()).split(b"\n")[0::4]
+    assert sum(h.endswith(b" cor") for h in heads) >= len(heads) // 3   # (a third of the reads corrected, in the reference's own output)
+
+
 @pytest.mark.parametrize("name", ["qv_pair/straddle", "qv_ends/straddle", "qv_dense_mfk2/straddle", "qv_dense_mfk1/straddle", "qv_mixed_pe/straddle",
                                   "qv_mixed_il/straddle", "qv_lengths/straddle", "qv_pair_k32/straddle", "qv_mixed_pe/fasta"])
 def test_oracle_cli_equals_reference_where_qualities_decide(oracle, name, tmp_path):
