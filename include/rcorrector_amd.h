@@ -159,6 +159,27 @@ int rc_table_count_spectrum(rc_ctx *ctx, uint32_t max_bin);
  * stats may be NULL. */
 int rc_table_spectrum(rc_ctx *ctx, int source, uint64_t *freq, uint32_t max_bin, rc_spectrum_stats *stats);
 
+/* ---- two tables side by side: the joint count matrix of their k-mers (what `kat comp` computes from two Jellyfish hashes) ------
+ * cells is the caller's array of (max_bin + 1)^2 words, max_bin 1 .. 1023 (at most 8 MiB on the device: a limit of this
+ * call): cells[i * (max_bin + 1) + j] = the number of distinct canonical k-mers whose count in a's table folds to i and
+ * whose count in b's folds to j -- folded as rc_table_spectrum folds (exact below max_bin, the last bin "at least
+ * max_bin"), bin 0 = the table does not hold the k-mer; cells[0] = 0.  An entry is what rc_table_spectrum(source 0)
+ * counts: a live entry with the count rc_table_lookup returns (the full count of a PACKED table's prefix included).  The
+ * statistics are exact whatever max_bin is; stats may be NULL.
+ * Any two tables of the same k on the same device: built, loaded, counted, shared (rc_table_share) or replicated, of any
+ * layout each; a == b is allowed (a diagonal matrix).  Both contexts are drained first (their queued batches complete);
+ * the kernels run on a's stream and the call is complete on return.  Neither table is changed (rc_table_digest stays).
+ * RC_STATUS_STATE: a context without a table.  RC_STATUS_ARG: different k, contexts on different devices (bring one
+ * table over with rc_table_replicate), cells NULL, max_bin out of range.  The error text is a's (rc_last_error(a)).
+ * No reference counterpart. */
+typedef struct {
+    uint64_t distinct_a, distinct_b, shared;   /* distinct canonical k-mers; shared = held by both */
+    uint64_t mass_a, mass_b;                   /* sum of the counts (exact, not folded) */
+    uint64_t shared_mass_a, shared_mass_b;     /* a's / b's counts summed over the shared k-mers */
+    uint64_t max_count_a, max_count_b;
+} rc_table_compare_stats;
+int rc_table_compare(rc_ctx *a, rc_ctx *b, uint32_t max_bin, uint64_t *cells, rc_table_compare_stats *stats);
+
 /* ---- recount session: the k-mer spectrum of reads AFTER correction, and a census of the k-mers the table does not hold ------
  * A second, read-only use of the k-mer counter.  Between rc_recount_begin and rc_recount_finish the session collects arenas of
  * reads (NUL-separated, each arena < 2^32 bytes) in HBM, one byte per base; finish counts them by the counter's rules -- canonical

@@ -15,7 +15,7 @@ ABI_SYMBOLS = [
     "rc_table_count_begin", "rc_table_count_add", "rc_table_count_add_device", "rc_table_count_finish",
     "rc_table_count_keep", "rc_table_count_arenas", "rc_table_count_release", "rc_table_count_park", "rc_table_count_finish_sharded", "rc_submit_resident", "rc_wait_resident",
     "rc_table_count_reads_device", "rc_table_write_jfdump", "rc_table_share", "rc_table_replicate", "rc_table_replicate_async", "rc_table_lookup", "rc_table_export", "rc_table_digest", "rc_table_layout", "rc_table_stats",
-    "rc_table_count_spectrum", "rc_table_spectrum",
+    "rc_table_count_spectrum", "rc_table_spectrum", "rc_table_compare",
     "rc_recount_begin", "rc_recount_add", "rc_recount_add_device", "rc_recount_follow", "rc_recount_finish",
     "rc_change_report_begin", "rc_change_report_get", "rc_change_report_end",
     "rc_weak_profile_device", "rc_weak_profile_into",
@@ -77,6 +77,14 @@ class _ResidentBatch(C.Structure):
 
 class _SpectrumStats(C.Structure):
     _fields_ = [("distinct", C.c_uint64), ("total", C.c_uint64), ("unique", C.c_uint64), ("max_count", C.c_uint64)]
+
+
+COMPARE_FIELDS = ("distinct_a", "distinct_b", "shared", "mass_a", "mass_b", "shared_mass_a", "shared_mass_b", "max_count_a", "max_count_b")
+
+
+class _CompareStats(C.Structure):
+    """rc_table_compare_stats: nine counts"""
+    _fields_ = [(f, C.c_uint64) for f in COMPARE_FIELDS]
 
 
 class _RecountStats(C.Structure):
@@ -236,6 +244,7 @@ def load_library():
     L.rc_table_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rc_table_count_spectrum.argtypes = [vp, C.c_uint32]
     L.rc_table_spectrum.argtypes = [vp, C.c_int, vp, C.c_uint32, C.POINTER(_SpectrumStats)]
+    L.rc_table_compare.argtypes = [vp, vp, C.c_uint32, vp, C.POINTER(_CompareStats)]
     L.rc_recount_begin.argtypes = [vp, C.c_uint32]
     L.rc_recount_add.argtypes = [vp, vp, C.c_size_t]
     L.rc_recount_add_device.argtypes = [vp, vp, C.c_size_t]
@@ -482,6 +491,19 @@ class Context:
         st = _SpectrumStats()
         self._ck(self._L.rc_table_spectrum(self._h, src, freq.ctypes.data, int(max_bin), C.byref(st)))
         return freq, {"distinct": st.distinct, "total": st.total, "unique": st.unique, "max_count": st.max_count}
+
+    # ---- two tables side by side ----
+    def table_compare(self, other, max_bin=255):
+        """rc_table_compare: this context's table (a) against `other`'s (b; same k, same device; may be this context) --
+        {"cells": uint64 array (max_bin + 1, max_bin + 1), cells[i, j] = distinct canonical k-mers whose count folds to i here
+        and to j there (0: not held; the last bin: at least max_bin), and the fields of rc_table_compare_stats as ints}."""
+        n = int(max_bin) + 1 if 1 <= int(max_bin) <= 1023 else 1   # (a max_bin out of range: the library refuses it)
+        cells = np.zeros((n, n), dtype=np.uint64)
+        st = _CompareStats()
+        self._ck(self._L.rc_table_compare(self._h, other._h, int(max_bin) & 0xFFFFFFFF, cells.ctypes.data, C.byref(st)))
+        out = {f: int(getattr(st, f)) for f in COMPARE_FIELDS}
+        out["cells"] = cells
+        return out
 
     # ---- recount session: the spectrum of reads after correction, and the k-mers the table does not hold ----
     def recount_begin(self, max_bin=10000):
