@@ -44,14 +44,15 @@ void rc_table_release(rc_ctx *ctx)
         }
     }
     if (ctx->d_buckets && !ctx->buckets_borrowed) (void)hipFree(reinterpret_cast<char *>(ctx->d_buckets) - RC_TABLE_PREFIX_BYTES);
-    ctx->d_buckets = nullptr;
+    rc_table_desc &t = ctx->table();  // (the geometry of the table that went stays readable: rc_table_stats)
+    t.d_buckets = nullptr;
+    t.filter_words = 0;
+    t.table_bytes = 0;
+    t.n_entries = 0;
     ctx->buckets_borrowed = false;
     if (ctx->counted_codes) (void)hipFree(ctx->counted_codes);
     ctx->counted_codes = nullptr;
     ctx->counted_n = 0;
-    ctx->filter_words = 0;
-    ctx->table_bytes = 0;
-    ctx->n_entries = 0;
 }
 
 int rc_drain(rc_ctx *ctx)
@@ -63,19 +64,75 @@ int rc_drain(rc_ctx *ctx)
     return RC_OK;
 }
 
+int rc_copy_across(rc_ctx *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t n, hipStream_t st, const char *what)
+{
+    if (n == 0) return RC_OK;
+    if (!getenv("RC_REPLICATE_STAGED")) {  // (tests set it: the path of GPUs without peer access)
+        if (dst_dev == src_dev) {
+            RC_CHECK_HIP(ctx, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, st));
+            return RC_OK;
+        }
+        int can = 0;
+        if (hipDeviceCanAccessPeer(&can, dst_dev, src_dev) != hipSuccess) can = 0;
+        if (can) {
+            const hipError_t e = hipDeviceEnablePeerAccess(src_dev, 0);  // (dst_dev is the current device)
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) can = 0;
+            (void)hipGetLastError();
+        }
+        if (can) {
+            RC_CHECK_HIP(ctx, hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, n, st));
+            return RC_OK;
+        }
+    }
+    // no direct path between the two GPUs: through page-locked host memory, two pieces in flight
+    const size_t CH = (size_t)64 << 20;
+    const int nbuf = n > CH ? 2 : 1;
+    char *h[2] = {nullptr, nullptr};
+    hipEvent_t up[2] = {nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < nbuf && e == hipSuccess; ++i) {
+        e = hipHostMalloc((void **)&h[i], std::min(CH, n), hipHostMallocPortable);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&up[i], hipEventDisableTiming);
+    }
+    size_t piece = 0;
+    for (size_t at = 0; at < n && e == hipSuccess; at += CH, ++piece) {
+        const size_t m = std::min(CH, n - at);
+        const int b = (int)(piece & 1);
+        if (piece >= 2) e = hipEventSynchronize(up[b]);  // the upload that last used this buffer
+        if (e == hipSuccess) e = hipSetDevice(src_dev);
+        if (e == hipSuccess) e = hipMemcpy(h[b], (const char *)src + at, m, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipSetDevice(dst_dev);
+        if (e == hipSuccess) e = hipMemcpyAsync((char *)dst + at, h[b], m, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipEventRecord(up[b], st);
+    }
+    (void)hipSetDevice(dst_dev);
+    const hipError_t arrived = hipStreamSynchronize(st);  // (the buffers go, and the caller may count on the bytes)
+    if (e == hipSuccess) e = arrived;
+    for (int i = 0; i < 2; ++i) {
+        if (h[i]) (void)hipHostFree(h[i]);
+        if (up[i]) (void)hipEventDestroy(up[i]);
+    }
+    if (e != hipSuccess) {
+        rc_set_error(ctx, "%s failed: %s", what, hipGetErrorString(e));
+        return RC_ERR_HIP;
+    }
+    return RC_OK;
+}
+
 rc_table_view rc_view(const rc_ctx *ctx)
 {
+    const rc_table_desc &t = ctx->table();
     rc_table_view v;
-    v.buckets = ctx->d_buckets;
-    v.nb_home = ctx->nb_home;
-    v.nbuckets_alloc = ctx->nb_alloc;
-    v.layout = ctx->layout;
-    v.ext = ctx->ext;
+    v.buckets = t.d_buckets;
+    v.nb_home = t.nb_home;
+    v.nbuckets_alloc = t.nb_alloc;
+    v.layout = t.layout;
+    v.ext = t.ext;
     v.k = ctx->k;
-    v.filter_words = ctx->filter_words;
-    v.filter = ctx->filter_words ? ctx->d_buckets + ctx->table_bytes / 4 : nullptr;
-    v.filter_kind = ctx->filter_kind;
-    v.filter_all = ctx->filter_all;
+    v.filter_words = t.filter_words;
+    v.filter = t.filter_words ? t.d_buckets + t.table_bytes / 4 : nullptr;
+    v.filter_kind = t.filter_kind;
+    v.filter_all = t.filter_all;
     return v;
 }
 
@@ -133,17 +190,8 @@ rc_ctx *rc_slot_lane(rc_ctx *ctx, int slot, bool create, bool refresh)
         ln->lane_parent = ctx;
     }
     if (refresh) {  // plain assignments: the table (borrowed, as rc_table_share lends it), the parameters, the mode, the kept arenas
-        ln->d_buckets = ctx->d_buckets;
+        ln->table() = ctx->table();
         ln->buckets_borrowed = true;
-        ln->nb_home = ctx->nb_home;
-        ln->layout = ctx->layout;
-        ln->ext = ctx->ext;
-        ln->nb_alloc = ctx->nb_alloc;
-        ln->n_entries = ctx->n_entries;
-        ln->table_bytes = ctx->table_bytes;
-        ln->filter_words = ctx->filter_words;
-        ln->filter_kind = ctx->filter_kind;
-        ln->filter_all = ctx->filter_all;
         ln->P = ctx->P;
         ln->params_set = ctx->params_set;
         ln->qual_bits = ctx->qual_bits;

@@ -14,18 +14,7 @@
 
 #include "../../include/rcorrector_amd.h"
 #include "rc_internal.h"
-
-// parsed dump kept between rc_table_load_jfdump() and rc_estimate_error_rate()
-struct rc_dump_cache {
-    // forward code of every entry (file order), main.cpp:326-328, and a flag "holds a non-ACGT
-    // letter before its last base" -- kept in the chunks the parser threads produced (concatenating
-    // a few hundred MB on one thread cost more than parsing them on thirty-two)
-    std::vector<std::vector<uint64_t>> codes;
-    std::vector<std::vector<int8_t>> inv_mid;
-    size_t n = 0;
-    int load_state_invalid = 0;   // validity of the KmerCode object the load pass leaves behind
-    bool valid = false;
-};
+#include "rc_jfdump.h"
 
 struct rc_ctx_full : rc_ctx {
     rc_dump_cache dump;

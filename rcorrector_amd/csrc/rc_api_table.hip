@@ -29,258 +29,49 @@ int rc_table_build(rc_ctx *ctx, const uint64_t *codes, const int32_t *counts, si
     return rc_table_build_device(ctx, b_codes.as<uint64_t>(), b_counts.as<int32_t>(), n);
 }
 
-// main.cpp:294-308.  Tokens are whitespace separated (fscanf "%s"); the first of a pair is
-// ">COUNT" (atoi of the text after the first character), the second the k-mer, pushed through
-// KmerCode::Append character by character (only the last k characters survive the mask).
+// n x Store::Put in file order: the pieces go to the device one after the other, no host copy
+static int dump_upload_and_build(rc_ctx *ctx, const std::vector<rc_dump_piece> &pieces, size_t n_put)
+{
+    rc_dev_tmp b_codes, b_counts;
+    RC_CHECK_HIP(ctx, b_codes.alloc(n_put * 8));
+    RC_CHECK_HIP(ctx, b_counts.alloc(n_put * 4));
+    size_t at = 0;
+    for (const rc_dump_piece &P : pieces) {
+        const size_t m = P.put_codes.size();
+        if (m) {
+            RC_CHECK_HIP(ctx, hipMemcpyAsync(b_codes.as<uint64_t>() + at, P.put_codes.data(), m * 8, hipMemcpyHostToDevice, ctx->stream));
+            RC_CHECK_HIP(ctx, hipMemcpyAsync(b_counts.as<int32_t>() + at, P.put_counts.data(), m * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
+        at += m;
+    }
+    const int rc = rc_table_build_device(ctx, b_codes.as<uint64_t>(), b_counts.as<int32_t>(), n_put);
+    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (the pieces' host arrays go with the caller's vector)
+    return rc;
+}
+
+// main.cpp:294-308: the text (rc_jfdump.h) read, parsed on several host threads and joined in file order, then the table
 int rc_table_load_jfdump(rc_ctx *c, const char *path, int64_t *stored)
 {
     if (!c || !path) return RC_ERR_ARG;
     rc_ctx_full *ctx = static_cast<rc_ctx_full *>(c);
     RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    FILE *fp = fopen(path, "rb");
-    if (!fp) {
-        rc_set_error(ctx, "Could not open file %s", path);
-        return RC_ERR_IO;
+    rc_dump_text text;
+    char err[512];
+    if (const int rc = rc_dump_read_file(path, &text, err, sizeof err)) {
+        rc_set_error(ctx, "%s", err);
+        return rc;
     }
-    fseek(fp, 0, SEEK_END);
-    long sz = ftell(fp);
-    fseek(fp, 0, SEEK_SET);
-    // the whole text, uninitialised and read by several threads at once (pread into disjoint slices:
-    // a single reader is bound by the copy out of the page cache)
-    struct text_buf {
-        char *p = nullptr;
-        ~text_buf() { free(p); }
-        char *data() { return p; }
-        char &operator[](size_t i) { return p[i]; }
-    } buf;
-    buf.p = (char *)malloc((size_t)sz + 1);
-    if (!buf.p) {
-        fclose(fp);
-        rc_set_error(ctx, "out of memory reading %s (%ld bytes)", path, sz);
-        return RC_ERR_NOMEM;
-    }
-    {
-        const int fd = fileno(fp);
-        unsigned RT = std::thread::hardware_concurrency();
-        if (RT == 0) RT = 4;
-        if (RT > 32) RT = 32;
-        if ((size_t)sz < ((size_t)8 << 20)) RT = 1;
-        std::vector<char> ok(RT, 1);
-        auto rd = [&](unsigned t) {
-            size_t at = (size_t)sz * t / RT;
-            const size_t hi = (size_t)sz * (t + 1) / RT;
-            while (at < hi) {
-                const ssize_t n = pread(fd, buf.p + at, hi - at, (off_t)at);
-                if (n <= 0) {
-                    ok[t] = 0;
-                    return;
-                }
-                at += (size_t)n;
-            }
-        };
-        if (RT == 1) {
-            rd(0);
-        } else {
-            std::vector<std::thread> th;
-            for (unsigned t = 0; t < RT; ++t) th.emplace_back(rd, t);
-            for (auto &x : th) x.join();
-        }
-        fclose(fp);
-        for (unsigned t = 0; t < RT; ++t)
-            if (!ok[t]) {
-                rc_set_error(ctx, "short read on %s", path);
-                return RC_ERR_IO;
-            }
-    }
-    buf[(size_t)sz] = 0;
-    const bool tm = ctx->env_timing;
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_read = now();
-
-    const int k = ctx->k;
-    const uint64_t mask = rc_kmer_mask(k);
-    rc_dump_cache &D = ctx->dump;
-    D.codes.clear();
-    D.inv_mid.clear();
-    D.n = 0;
-    D.load_state_invalid = 0;
-    auto is_ws = [](char ch) { return ch == ' ' || ch == '\n' || ch == '\t' || ch == '\r' || ch == '\f' || ch == '\v'; };
-
-    // the text is cut at entry starts ('>' right after white space) and the pieces are parsed by
-    // several host threads; the per-piece results are concatenated in file order
-    struct piece {
-        std::vector<uint64_t> codes, put_codes;
-        std::vector<int8_t> inv_mid;
-        std::vector<int32_t> put_counts;
-        int64_t accepted = 0;
-        int last_state_invalid = -1;  // -1: no accepted entry in this piece
-    };
-    unsigned T = std::thread::hardware_concurrency();
-    if (T == 0) T = 4;
-    if (T > 32) T = 32;
-    if ((size_t)sz < (1u << 20)) T = 1;
-    std::vector<size_t> cut(T + 1, (size_t)sz);
-    cut[0] = 0;
-    for (unsigned t = 1; t < T; ++t) {
-        size_t pos = (size_t)sz * t / T;
-        if (pos < cut[t - 1]) pos = cut[t - 1];
-        while (pos < (size_t)sz && !(buf[pos] == '>' && (pos == 0 || is_ws(buf[pos - 1])))) ++pos;
-        cut[t] = pos;
-    }
-    std::vector<piece> pieces(T);
-    int8_t base_code[256];
-    memset(base_code, -1, sizeof base_code);
-    base_code[(unsigned char)'A'] = 0;
-    base_code[(unsigned char)'C'] = 1;
-    base_code[(unsigned char)'G'] = 2;
-    base_code[(unsigned char)'T'] = 3;
-    // atoi() as glibc implements it, (int)strtol(): the long value saturates at LONG_MAX / LONG_MIN and
-    // the conversion to int keeps its low 32 bits (main.cpp:297 applies it to the count token)
-    auto atoi_of = [](unsigned long long v, bool ovf, bool neg) -> int {
-        long long lv;
-        if (ovf)
-            lv = neg ? (long long)0x8000000000000000ULL : 0x7fffffffffffffffLL;
-        else
-            lv = neg ? -(long long)v : (long long)v;
-        return (int)(uint32_t)(uint64_t)lv;
-    };
-    auto parse = [&](unsigned t) {
-        piece &P = pieces[t];
-        const char *p = buf.data() + cut[t], *end = buf.data() + cut[t + 1];
-        const size_t guess = (size_t)(end - p) / (size_t)(k + 4) + 16;
-        P.codes.reserve(guess);
-        P.inv_mid.reserve(guess);
-        P.put_codes.reserve(guess);
-        P.put_counts.reserve(guess);
-        while (true) {
-            // fast path for the layout `jellyfish dump` writes: ">DIGITS\nKMER\n" with exactly k
-            // letters out of ACGT -- everything else goes through the general tokeniser below,
-            // which is what defines the result
-            if (p < end && *p == '>' && p + 1 < end && (unsigned)(p[1] - '0') <= 9u) {
-                const char *q = p + 1;
-                unsigned long long v = 0;
-                bool ovf = false;
-                while (q < end && (unsigned)(*q - '0') <= 9u) {
-                    const unsigned d = (unsigned)(*q - '0');
-                    if (v > (0x7fffffffffffffffULL - d) / 10) ovf = true;
-                    if (!ovf) v = v * 10 + d;
-                    ++q;
-                }
-                const int cnt = atoi_of(v, ovf, false);
-                if (q < end && *q == '\n' && q + 1 + k < end && q[1 + k] == '\n') {
-                    const unsigned char *s2 = reinterpret_cast<const unsigned char *>(q + 1);
-                    uint64_t code = 0;
-                    int bad = 0;
-                    for (int i = 0; i < k; ++i) {
-                        const int b = base_code[s2[i]];
-                        bad |= b;
-                        code = (code << 2) | (uint64_t)(b & 3);
-                    }
-                    if (bad >= 0) {  // all four codes are non-negative: no other letter in the k-mer
-                        p = q + 2 + k;
-                        P.codes.push_back(code);
-                        P.inv_mid.push_back(0);
-                        if (cnt <= 1) continue;
-                        P.last_state_invalid = 0;
-                        ++P.accepted;
-                        P.put_codes.push_back(code);
-                        P.put_counts.push_back((int32_t)cnt);
-                        continue;
-                    }
-                }
-            }
-            while (p < end && is_ws(*p)) ++p;
-            if (p >= end) break;
-            const char *t0 = p;
-            while (p < end && !is_ws(*p)) ++p;
-            int cnt = 0;  // atoi(&token[1])
-            {
-                const char *q = t0 + 1;
-                bool neg = false, ovf = false;
-                unsigned long long v = 0;
-                if (q < p && (*q == '-' || *q == '+')) {
-                    neg = *q == '-';
-                    ++q;
-                }
-                while (q < p && *q >= '0' && *q <= '9') {
-                    const unsigned d = (unsigned)(*q - '0');
-                    if (v > (0x7fffffffffffffffULL - d) / 10) ovf = true;
-                    if (!ovf) v = v * 10 + d;
-                    ++q;
-                }
-                cnt = atoi_of(v, ovf, neg);
-            }
-            while (p < end && is_ws(*p)) ++p;
-            const char *k0 = p;
-            while (p < end && !is_ws(*p)) ++p;
-            uint64_t code = 0;
-            int inv = -1;
-            for (const char *q = k0; q < p; ++q) {
-                int b;
-                switch (*q) {
-                case 'A': b = 0; break;
-                case 'C': b = 1; break;
-                case 'G': b = 2; break;
-                case 'T': b = 3; break;
-                default: b = -1;
-                }
-                if (inv != -1) ++inv;
-                code = ((code << 2) & mask) | (uint64_t)(b & 3);
-                if (b == -1) inv = 0;
-                if (inv >= k) inv = -1;
-            }
-            P.codes.push_back(code);
-            P.inv_mid.push_back(inv > 0 ? 1 : 0);
-            if (cnt <= 1) continue;
-            P.last_state_invalid = (inv != -1);
-            ++P.accepted;
-            if (inv == -1) {  // Store::Put ignores invalid k-mers, Store.h:53-54
-                P.put_codes.push_back(code);
-                P.put_counts.push_back((int32_t)cnt);
-            }
-        }
-    };
-    if (T == 1) {
-        parse(0);
-    } else {
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < T; ++t) th.emplace_back(parse, t);
-        for (auto &x : th) x.join();
-    }
-    int64_t accepted = 0;
+    std::vector<rc_dump_piece> pieces = rc_dump_parse(text.p, text.n, ctx->k, rc_host_threads(text.n, (size_t)1 << 20));
     size_t n_put = 0;
-    for (auto &P : pieces) {
-        D.n += P.codes.size();
-        n_put += P.put_codes.size();
-        accepted += P.accepted;
-        if (P.last_state_invalid >= 0) D.load_state_invalid = P.last_state_invalid;
-    }
+    int64_t accepted = 0;
+    rc_dump_join(pieces, &ctx->dump, &n_put, &accepted);  // (dump.valid == false from here until the table stands)
     const double t_parse = now();
     if (stored) *stored = accepted;
-    // n x Store::Put in file order: the pieces go to the device one after the other, no host copy
-    int rc = RC_OK;
-    {
-        rc_dev_tmp b_codes, b_counts;
-        RC_CHECK_HIP(ctx, b_codes.alloc(n_put * 8));
-        RC_CHECK_HIP(ctx, b_counts.alloc(n_put * 4));
-        size_t at = 0;
-        for (auto &P : pieces) {
-            const size_t m = P.put_codes.size();
-            if (m) {
-                RC_CHECK_HIP(ctx, hipMemcpyAsync(b_codes.as<uint64_t>() + at, P.put_codes.data(), m * 8, hipMemcpyHostToDevice, ctx->stream));
-                RC_CHECK_HIP(ctx, hipMemcpyAsync(b_counts.as<int32_t>() + at, P.put_counts.data(), m * 4, hipMemcpyHostToDevice, ctx->stream));
-            }
-            at += m;
-        }
-        rc = rc_table_build_device(ctx, b_codes.as<uint64_t>(), b_counts.as<int32_t>(), n_put);
-        RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the pieces' host arrays are released below
-    }
-    for (auto &P : pieces) {
-        D.codes.emplace_back(std::move(P.codes));
-        D.inv_mid.emplace_back(std::move(P.inv_mid));
-    }
-    if (tm) fprintf(stderr, "[rc timing] dump: parse %.2f s, table build %.2f s\n", t_parse - t_read, now() - t_parse);
-    D.valid = rc == RC_OK;  // (rc_table_build drops the cache of an earlier dump)
+    const int rc = dump_upload_and_build(ctx, pieces, n_put);
+    if (ctx->env_timing) fprintf(stderr, "[rc timing] dump: parse %.2f s, table build %.2f s\n", t_parse - t_read, now() - t_parse);
+    ctx->dump.valid = rc == RC_OK;  // (rc_table_build_device drops the cache of an earlier dump)
     return rc;
 }
 
@@ -297,17 +88,8 @@ int rc_table_share(rc_ctx *dst, const rc_ctx *src)
     }
     RC_CHECK_HIP(dst, hipSetDevice(dst->device));
     rc_table_release(dst);
-    dst->d_buckets = src->d_buckets;
+    dst->table() = src->table();
     dst->buckets_borrowed = true;
-    dst->nb_home = src->nb_home;
-    dst->layout = src->layout;
-    dst->ext = src->ext;
-    dst->nb_alloc = src->nb_alloc;
-    dst->n_entries = src->n_entries;
-    dst->table_bytes = src->table_bytes;
-    dst->filter_words = src->filter_words;
-    dst->filter_kind = src->filter_kind;
-    dst->filter_all = src->filter_all;
     return RC_OK;
 }
 
@@ -337,67 +119,10 @@ int rc_table_replicate_async(rc_ctx *dst, const rc_ctx *src)
     char *base = guard.as<char>();
     const char *from = reinterpret_cast<const char *>(src->d_buckets) - RC_TABLE_PREFIX_BYTES;
     // the bucket array (and its prefix) is the table
-    bool staged = getenv("RC_REPLICATE_STAGED") != nullptr;  // tests: the path of GPUs without peer access
-    if (src->device == dst->device) {
-        if (!staged) RC_CHECK_HIP(dst, hipMemcpyAsync(base, from, bytes, hipMemcpyDeviceToDevice, dst->stream));
-    } else if (!staged) {
-        int can = 0;
-        if (hipDeviceCanAccessPeer(&can, dst->device, src->device) != hipSuccess) can = 0;
-        if (can) {
-            const hipError_t e = hipDeviceEnablePeerAccess(src->device, 0);  // (dst is the current device)
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) can = 0;
-            (void)hipGetLastError();
-        }
-        if (can)
-            RC_CHECK_HIP(dst, hipMemcpyPeerAsync(base, dst->device, from, src->device, bytes, dst->stream));
-        else
-            staged = true;
-    }
-    if (staged) {  // no direct path between the two GPUs: through page-locked host memory, two pieces in flight
-        const size_t CH = (size_t)64 << 20;
-        char *h[2] = {nullptr, nullptr};
-        hipEvent_t up[2] = {nullptr, nullptr};
-        int rc = RC_OK;
-        auto fail = [&](hipError_t e, const char *what) {
-            rc_set_error(dst, "table_replicate: %s failed: %s", what, hipGetErrorString(e));
-            rc = RC_ERR_HIP;
-        };
-        for (int i = 0; i < 2 && rc == RC_OK; ++i) {
-            hipError_t e = hipHostMalloc((void **)&h[i], CH, hipHostMallocPortable);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&up[i], hipEventDisableTiming);
-            if (e != hipSuccess) fail(e, "hipHostMalloc");
-        }
-        size_t piece = 0;
-        for (size_t at = 0; at < bytes && rc == RC_OK; at += CH, ++piece) {
-            const size_t n = std::min(CH, bytes - at);
-            const int b = (int)(piece & 1);
-            hipError_t e = piece >= 2 ? hipEventSynchronize(up[b]) : hipSuccess;  // the upload that last used this buffer
-            if (e == hipSuccess) e = hipSetDevice(src->device);
-            if (e == hipSuccess) e = hipMemcpy(h[b], from + at, n, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipSetDevice(dst->device);
-            if (e == hipSuccess) e = hipMemcpyAsync(base + at, h[b], n, hipMemcpyHostToDevice, dst->stream);
-            if (e == hipSuccess) e = hipEventRecord(up[b], dst->stream);
-            if (e != hipSuccess) fail(e, "staged copy");
-        }
-        (void)hipSetDevice(dst->device);
-        (void)hipStreamSynchronize(dst->stream);
-        for (int i = 0; i < 2; ++i) {
-            if (h[i]) (void)hipHostFree(h[i]);
-            if (up[i]) (void)hipEventDestroy(up[i]);
-        }
-        if (rc) return rc;
-    }
+    if (const int rc = rc_copy_across(dst, base, dst->device, from, src->device, bytes, dst->stream, "table_replicate: staged copy")) return rc;
+    dst->table() = src->table();
     dst->d_buckets = reinterpret_cast<uint32_t *>(base + RC_TABLE_PREFIX_BYTES);
     guard.p = nullptr;  // (dst owns it now)
-    dst->nb_home = src->nb_home;
-    dst->layout = src->layout;
-    dst->ext = src->ext;
-    dst->nb_alloc = src->nb_alloc;
-    dst->n_entries = src->n_entries;
-    dst->table_bytes = src->table_bytes;
-    dst->filter_words = src->filter_words;
-    dst->filter_kind = src->filter_kind;
-    dst->filter_all = src->filter_all;
     return RC_OK;
 }
 
@@ -512,9 +237,7 @@ int rc_table_write_jfdump(rc_ctx *ctx, const char *path, int64_t *n_written)
     }
     const int k = ctx->k;
     const size_t n = codes.size();
-    unsigned T = std::thread::hardware_concurrency();
-    if (T == 0) T = 4;
-    if (T > 32) T = 32;
+    const unsigned T = rc_host_threads(n, 0);
     const size_t CH = 1u << 20;  // entries formatted per round and thread
     std::vector<std::vector<char>> out(T);
     bool ok = true;
@@ -523,27 +246,7 @@ int rc_table_write_jfdump(rc_ctx *ctx, const char *path, int64_t *n_written)
         for (unsigned t = 0; t < T; ++t) {
             const size_t lo = std::min(n, base + (size_t)t * CH), hi = std::min(n, lo + CH);
             out[t].clear();
-            if (lo >= hi) continue;
-            th.emplace_back([&, t, lo, hi]() {
-                std::vector<char> &o = out[t];
-                o.resize((hi - lo) * (size_t)(k + 14));
-                char *w = o.data();
-                for (size_t i = lo; i < hi; ++i) {
-                    *w++ = '>';
-                    char tmp[12];
-                    int nd = 0;
-                    uint32_t v = (uint32_t)counts[i];
-                    do {
-                        tmp[nd++] = (char)('0' + v % 10);
-                        v /= 10;
-                    } while (v);
-                    while (nd) *w++ = tmp[--nd];
-                    *w++ = '\n';
-                    for (int j = k - 1; j >= 0; --j) *w++ = "ACGT"[(codes[i] >> (2 * j)) & 3];
-                    *w++ = '\n';
-                }
-                o.resize((size_t)(w - o.data()));
-            });
+            if (lo < hi) th.emplace_back(rc_dump_format, codes.data(), counts.data(), lo, hi, k, &out[t]);
         }
         for (auto &x : th) x.join();
         for (unsigned t = 0; t < T && ok; ++t)
@@ -840,19 +543,7 @@ int rc_estimate_error_rate(rc_ctx *c, double wk, double *rate_out)
         if (rc) return rc;
     } else {
         const rc_dump_cache &D = ctx->dump;
-        // an entry that leaves an invalid KmerCode behind ends the scan (the IsValid() test at main.cpp:323)
-        size_t n = 0;
-        bool cut = D.load_state_invalid != 0;
-        for (size_t c = 0; c < D.inv_mid.size() && !cut; ++c) {
-            const std::vector<int8_t> &inv = D.inv_mid[c];
-            const void *hit = inv.empty() ? nullptr : memchr(inv.data(), 1, inv.size());
-            if (hit) {
-                n += (size_t)((const int8_t *)hit - inv.data());
-                cut = true;
-            } else {
-                n += inv.size();
-            }
-        }
+        const size_t n = rc_dump_scan_length(D);
         if (n) {
             rc_dev_tmp b_codes;
             RC_CHECK_HIP(ctx, b_codes.alloc(n * 8));

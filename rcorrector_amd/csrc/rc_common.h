@@ -22,6 +22,8 @@
 #define RC_HD inline
 #endif
 
+enum { RC_OK = 0, RC_ERR_ARG = -1, RC_ERR_HIP = -2, RC_ERR_IO = -3, RC_ERR_STATE = -4, RC_ERR_NOMEM = -5, RC_ERR_NOSPACE = -6 };
+
 #define RC_MAX_READ_LENGTH 1024  // utils.h:7 (reads hold <=1023 bases)
 #define RC_TRACE_WORDS 36         // int32 words per recorded iteration (rcorrector_amd.h: RC_TRACE_ITER_WORDS)
 #define RC_MAX_TRIAL 1025        // ErrorCorrection.cpp:7

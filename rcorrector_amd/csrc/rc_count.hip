@@ -593,50 +593,6 @@ int rc_recount_finish_session(rc_ctx *ctx, std::vector<uint64_t> *out)
 }
 
 // ---- the counter over several GPUs ---------------------------------------------------------------------------------------
-// n bytes from device memory of one GPU to device memory of another (or the same), queued on `st`, a stream of the destination's
-// device, which is the current one: device to device, peer to peer where the GPUs can, else through the host (synchronous)
-static int rc_copy_across(rc_ctx *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t n, hipStream_t st)
-{
-    if (n == 0) return RC_OK;
-    const bool force_staged = getenv("RC_REPLICATE_STAGED") != nullptr;  // tests: the path of GPUs without peer access
-    if (dst_dev == src_dev && !force_staged) {
-        RC_CHECK_HIP(ctx, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, st));
-        return RC_OK;
-    }
-    int can = 0;
-    if (!force_staged && dst_dev != src_dev) {
-        if (hipDeviceCanAccessPeer(&can, dst_dev, src_dev) != hipSuccess) can = 0;
-        if (can) {
-            const hipError_t e = hipDeviceEnablePeerAccess(src_dev, 0);
-            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) can = 0;
-            (void)hipGetLastError();
-        }
-    }
-    if (can) {
-        RC_CHECK_HIP(ctx, hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, n, st));
-        return RC_OK;
-    }
-    const size_t CH = (size_t)64 << 20;
-    char *h = nullptr;
-    RC_CHECK_HIP(ctx, hipHostMalloc((void **)&h, std::min(CH, n), hipHostMallocPortable));
-    hipError_t e = hipSuccess;
-    for (size_t at = 0; at < n && e == hipSuccess; at += CH) {
-        const size_t m = std::min(CH, n - at);
-        e = hipSetDevice(src_dev);
-        if (e == hipSuccess) e = hipMemcpy(h, (const char *)src + at, m, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipSetDevice(dst_dev);
-        if (e == hipSuccess) e = hipMemcpyAsync((char *)dst + at, h, m, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-    }
-    (void)hipSetDevice(dst_dev);
-    (void)hipHostFree(h);
-    if (e != hipSuccess) {
-        rc_set_error(ctx, "count: copy between GPUs failed: %s", hipGetErrorString(e));
-        return RC_ERR_HIP;
-    }
-    return RC_OK;
-}
-
 // rc_count_finish for reads that are spread over n contexts, one per GPU (`rcorrector -gpus N` in one pass: a batch's bases
 // are uploaded to the GPU that will correct it, and nowhere else).  The key space is cut into the P slices one GPU would
 // use; slice p belongs to GPU p % n: every GPU emits that slice's keys from its own arenas and sends them to the owner,
@@ -777,7 +733,7 @@ int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers)
                 const size_t m = (size_t)hist[(size_t)g][p];
                 if (g == o || m == 0) continue;
                 rc = rc_copy_across(c0, own[(size_t)o].S.keys + before_of(g, p), cs[o]->device, stage[(size_t)g].as<uint64_t>() + (size_t)o * stage_each[(size_t)g],
-                                    cs[g]->device, m * 8, cs[o]->stream);
+                                    cs[g]->device, m * 8, cs[o]->stream, "count: copy between GPUs");
                 if (rc) return rc;
             }
         }
@@ -842,8 +798,8 @@ int rc_count_finish_sharded(rc_ctx **cs, int n, int min_count, int64_t *n_kmers)
             const Piece &pc = pieces[p];
             if (pc.n == 0) continue;
             const rc_kept_arrays &K = own[(size_t)pc.owner].K;
-            int rc = rc_copy_across(c0, all.k.as<uint64_t>() + at, c0->device, K.k.as<uint64_t>() + pc.at, cs[pc.owner]->device, pc.n * 8, c0->stream);
-            if (!rc) rc = rc_copy_across(c0, all.c.as<int32_t>() + at, c0->device, K.c.as<int32_t>() + pc.at, cs[pc.owner]->device, pc.n * 4, c0->stream);
+            int rc = rc_copy_across(c0, all.k.as<uint64_t>() + at, c0->device, K.k.as<uint64_t>() + pc.at, cs[pc.owner]->device, pc.n * 8, c0->stream, "count: copy between GPUs");
+            if (!rc) rc = rc_copy_across(c0, all.c.as<int32_t>() + at, c0->device, K.c.as<int32_t>() + pc.at, cs[pc.owner]->device, pc.n * 4, c0->stream, "count: copy between GPUs");
             if (rc) return rc;
             at += pc.n;
         }

@@ -22,8 +22,6 @@
         }                                                                                        \
     } while (0)
 
-enum { RC_OK = 0, RC_ERR_ARG = -1, RC_ERR_HIP = -2, RC_ERR_IO = -3, RC_ERR_STATE = -4, RC_ERR_NOMEM = -5, RC_ERR_NOSPACE = -6 };
-
 // scoped device allocation: freed on every exit path of the function that owns it
 struct rc_dev_tmp {
     void *p = nullptr;
@@ -119,7 +117,24 @@ struct rc_kernel_timer {
 
 enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_TRUST_PLANES = 5, RC_T_TRUST = 6, RC_T_DEPTH = 7, RC_T_COUNT };
 
-struct rc_ctx {
+// what describes a k-mer table in HBM: a context that shares or copies another's table, or a slot lane its parent's, takes all of it
+// in one assignment, and rc_view reads nothing else (but k)
+struct rc_table_desc {
+    uint32_t *d_buckets = nullptr;
+    uint32_t nb_home = 0;
+    int layout = 0;       // slot layout of the table (rc_common.h): 0 WIDE, 1 PACKED
+    int ext = 0;          // PACKED: remainder bits kept above the count (rc_table_view::ext)
+    uint32_t nb_alloc = 0;
+    size_t n_entries = 0;   // accepted entries (duplicates included)
+    size_t table_bytes = 0;
+    uint32_t filter_words = 0;  // absence filter behind the bucket array (rc_common.h: rc_table_view::filter), 0 = none
+    int filter_kind = 0;        // rc_table_view::filter_kind of the filter that is there
+    int filter_all = 0;         // rc_table_view::filter_all
+    rc_table_desc &table() { return *this; }
+    const rc_table_desc &table() const { return *this; }
+};
+
+struct rc_ctx : rc_table_desc {
     int device = 0;
     int k = 23;
     int n_cu = 256;
@@ -144,27 +159,17 @@ struct rc_ctx {
     bool is_lane = false;
     bool env_slot_lanes = true;
 
-    // k-mer table in HBM
-    uint32_t *d_buckets = nullptr;
+    // k-mer table in HBM: its description is the base rc_table_desc
     bool buckets_borrowed = false;  // rc_table_share: another context owns d_buckets
-    uint32_t nb_home = 0;
     double table_load = 0.50;  // target slot load factor of the next build (WIDE layout)
     bool table_load_set = false;  // RC_TABLE_LOAD given: no size-dependent choice
     double table_load_packed = 0.50;  // ... (PACKED layout)
-    int layout = 0;       // slot layout of the table (rc_common.h): 0 WIDE, 1 PACKED
-    int ext = 0;          // PACKED: remainder bits kept above the count (rc_table_view::ext)
     int layout_pref = 1;  // 0: always WIDE (RC_TABLE_LAYOUT=wide)
-    uint32_t nb_alloc = 0;
-    size_t n_entries = 0;   // accepted entries (duplicates included)
-    size_t table_bytes = 0;
     // the canonical codes of the entries a table was counted from (rc_count_finish), kept until the ERROR_RATE pass has used them
     // or the table goes: that pass wants every entry's code, and reading them back out of the buckets (k_export: a decode and
     // a probe walk per slot) costs more than the 8 bytes per entry it frees
     void *counted_codes = nullptr;
     size_t counted_n = 0;
-    uint32_t filter_words = 0;  // absence filter behind the bucket array (rc_common.h: rc_table_view::filter), 0 = none
-    int filter_kind = 0;        // rc_table_view::filter_kind of the filter that is there
-    int filter_all = 0;         // rc_table_view::filter_all
 
     // -verbose support: iterations recorded per read by k_correct (0 = off) and the record buffer
     int trace_cap = 0;
@@ -310,6 +315,11 @@ void rc_table_release(rc_ctx *ctx);
 static inline rc_ctx *rc_home(rc_ctx *ctx) { return ctx->is_lane && ctx->lane_parent ? ctx->lane_parent : ctx; }
 // ctx's device current, and what ctx and its slot lanes (streams of their own) have queued has run
 int rc_drain(rc_ctx *ctx);
+// n bytes from device memory of GPU src_dev to device memory of GPU dst_dev (or the same), queued on `st`, a stream of dst_dev,
+// which is the current device: device to device, peer to peer where the GPUs can, else (or with RC_REPLICATE_STAGED set) through
+// page-locked host memory in 64 MB pieces, two in flight -- the bytes have then arrived on return, and a failure reads
+// "`what` failed: ..."
+int rc_copy_across(rc_ctx *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t n, hipStream_t st, const char *what);
 void rc_timer_begin(rc_ctx *ctx);
 void rc_timer_end(rc_ctx *ctx, int which);
 // f(std::bool_constant<ext>{}): the launch of a kernel that is compiled for tables with and without remainder-extension bits
