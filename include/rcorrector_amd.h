@@ -320,6 +320,42 @@ int rc_read_depth_device(rc_ctx *ctx, const uint8_t *d_seq, const uint32_t *d_of
  * Without one a submit launches, copies and allocates nothing for it.  RC_STATUS_ARG: a bad slot; RC_STATUS_STATE: no table. */
 int rc_read_depth_into(rc_ctx *ctx, int slot, rc_read_depth *out);
 
+/* ---- per-read screen: which reads hold the k-mers of a second set -------------------------------------------------------------
+ * rc_table_compare says how much of a library's k-mer mass an rRNA, mitochondrial, adapter or host set holds; this says which
+ * reads hold it -- the step taken right after correction (rRNA removal, host or PhiX decontamination), without a second aligner
+ * run: the reads are in HBM already, and the work is one probe per base into a second table.  For one read of L bases, at the
+ * context's k, against the table S of another context (the SCREEN context; it may be the same one) and a threshold min_count
+ * >= 1: window i (0 <= i <= L - k; none if L < k) is VALID exactly as for rc_read_weak above, and a valid window is a HIT if
+ * GetCount of its canonical k-mer in S (Store.h:59-66) is at least min_count.
+ *   valid    number of valid windows
+ *   hits     number of hit windows
+ *   covered  number of bases of the read that lie inside at least one hit window, 0 .. L
+ *   longest  the longest run of consecutive window positions that are all hits (an invalid window is no hit and ends a run);
+ *            such a run spans longest + k - 1 bases
+ * and four zeros for a read shorter than k.  hits <= valid, longest <= hits, and with hits > 0: longest + k - 1 <= covered <=
+ * min(L, hits * k).  Nothing is trimmed, dropped or reordered: the numbers only annotate.  No reference counterpart. */
+typedef struct { int32_t valid, hits, covered, longest; } rc_read_screen;   /* 16 bytes per read */
+/* The reads of an arena in HBM as they are (call it behind rc_correct_device for the corrected ones): d_out[r] for each of the
+ * n_reads reads, under rc_read_depth_device's rules for d_seq, d_off, offsets that leave the arena and max_read_len.
+ * Asynchronous on ctx's stream (rc_sync(ctx) to wait).  ctx supplies k, device and stream and needs no table of its own;
+ * `screen` must hold a table -- built, loaded, counted, shared or replicated, of either slot layout, whatever ctx's own is -- of
+ * the same k on the same device, is not changed, and must keep that table until the kernel has run.  RC_STATUS_ARG: a null
+ * pointer (screen; the others with n_reads > 0), an arena of 4 GiB or more, max_read_len above the library's 1 023 bases,
+ * min_count < 1, a screen context of another k or on another device; RC_STATUS_STATE: no table in `screen`.  rc_profile_get's
+ * kernel 8 (of ctx) times it. */
+int rc_read_screen_device(rc_ctx *ctx, const rc_ctx *screen, const uint8_t *d_seq, const uint32_t *d_off, uint32_t n_reads,
+                          uint64_t nbytes, int32_t max_read_len, int32_t min_count, rc_read_screen *d_out);
+/* One-shot, as rc_weak_profile_into and under the same rules: the NEXT batch submitted into `slot` also has its corrected
+ * reads screened against `screen`'s table, on the GPU behind its last correction kernel; out[total] (indexed like ret / l / m
+ * / h) holds them when that batch's wait returns success.  The submit consumes the registration whether it succeeds or not;
+ * out == NULL withdraws (screen and min_count are not looked at then); a page-locked `out` is written by DMA, any other by the
+ * wait that succeeds.  It may be armed together with the weak profile and the depth on one submit; one screen set per
+ * registration.  THE SCREEN CONTEXT AND ITS TABLE MUST STAY ALIVE AND UNCHANGED UNTIL THAT BATCH'S WAIT HAS RETURNED: the
+ * kernel reads the table where it lies.  Without a registration a submit launches, copies and allocates nothing for it.
+ * RC_STATUS_ARG: a bad slot, and with out != NULL a null screen, min_count < 1, another k or another device;
+ * RC_STATUS_STATE: no table in `screen`. */
+int rc_read_screen_into(rc_ctx *ctx, int slot, const rc_ctx *screen, int32_t min_count, rc_read_screen *out);
+
 /* ---- duplicate census: how many reads / pairs are exact copies of one another, before and after correction ------------------
  * A UNIT is a read (mode 0) or a pair (mode 1: read r of the first half and read r of the second; mode 2: reads 2u and 2u + 1 --
  * the mates of the correction report).  Two units are duplicates when their base strings are byte for byte equal: equal
@@ -794,7 +830,8 @@ int rc_profile_correct_counters(rc_ctx *ctx, uint64_t *reads_listed, uint64_t *g
  * (MAX_TRIAL, ErrorCorrection.cpp:7; the straggler of tools/find_straggler.py).  NULL switches it off. */
 int rc_profile_read_rounds(rc_ctx *ctx, int32_t *d_rounds);
 /* kernel 0 = probe, 1 = threshold, 2 = correct, 3 = isolated substitutions, 4 = weak-k-mer profile, 5 = the trust profile's
- * planes, 6 = its accumulate and column sums, 7 = per-read k-mer depth; accumulated since the last reset */
+ * planes, 6 = its accumulate and column sums, 7 = per-read k-mer depth, 8 = per-read screen against a second k-mer set;
+ * accumulated since the last reset */
 int rc_profile_get(rc_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
 int rc_profile_reset(rc_ctx *ctx);
 

@@ -20,6 +20,7 @@ ABI_SYMBOLS = [
     "rc_change_report_begin", "rc_change_report_get", "rc_change_report_end",
     "rc_weak_profile_device", "rc_weak_profile_into",
     "rc_read_depth_device", "rc_read_depth_into",
+    "rc_read_screen_device", "rc_read_screen_into",
     "rc_dup_census_begin", "rc_dup_census_get", "rc_dup_census_end", "rc_read_keys_device", "rc_dup_census_merge",
     "rc_recur_census_begin", "rc_recur_census_get", "rc_recur_census_end", "rc_recur_census_merge", "rc_change_keys_device",
     "rc_trust_profile_device", "rc_trust_profile_begin", "rc_trust_profile_get", "rc_trust_profile_end",
@@ -257,6 +258,8 @@ def load_library():
     L.rc_weak_profile_into.argtypes = [vp, C.c_int, vp, C.c_int32]
     L.rc_read_depth_device.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, vp]
     L.rc_read_depth_into.argtypes = [vp, C.c_int, vp]
+    L.rc_read_screen_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, vp]
+    L.rc_read_screen_into.argtypes = [vp, C.c_int, vp, C.c_int32, vp]
     L.rc_dup_census_begin.argtypes = [vp]
     L.rc_dup_census_get.argtypes = [vp, C.c_uint32, C.POINTER(_DupCensus)]
     L.rc_dup_census_end.argtypes = [vp]
@@ -605,6 +608,35 @@ class Context:
     def read_depth_withdraw(self, slot):
         """rc_read_depth_into(out = NULL): the next batch of `slot` has its depth not taken after all"""
         self._ck(self._L.rc_read_depth_into(self._h, int(slot), None))
+
+    # ---- per-read screen against a second k-mer set: valid and hit windows, covered bases, longest run of hits ----
+    def read_screen_device(self, screen, d_seq, d_off, n_reads, nbytes, max_read_len, d_out, min_count=1):
+        """rc_read_screen_device: the reads of an arena in HBM as they are against the table of `screen` (a Context of the same
+        k on the same device; it may be this one); d_out: device memory for n_reads x 4 int32 (valid, hits, covered, longest:
+        rc_read_screen).  Asynchronous: sync() to wait."""
+        self._ck(self._L.rc_read_screen_device(self._h, screen._h, _ptr(d_seq), _ptr(d_off), n_reads, nbytes, int(max_read_len), int(min_count),
+                                               _ptr(d_out)))
+
+    def read_screen_into(self, slot, total_reads, screen, min_count=1, out=None):
+        """rc_read_screen_into: the next batch submitted into `slot` (correct_batch: slot 0) also has its corrected reads
+        screened against the table of `screen`.  Returns a page-locked (total_reads, 4) int32 array -- columns valid, hits,
+        covered, longest, rows indexed like ret / l / m / h -- that the batch's wait fills (out: a C-contiguous int32 array of
+        that shape to fill instead, e.g. a pageable one).  One shot: every submit consumes the registration.  `screen` must
+        keep its table until that wait; this context holds on to it until the next registration of the slot."""
+        total_reads = int(total_reads)
+        if out is None:
+            out = self.host_array(total_reads * 4, dtype=np.int32).reshape(total_reads, 4)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.shape == (total_reads, 4)):
+            raise TypeError("out must be a C-contiguous int32 numpy array of shape (total_reads, 4)")
+        self._ck(self._L.rc_read_screen_into(self._h, int(slot), screen._h, int(min_count), out.ctypes.data))
+        if not hasattr(self, "_screen_out"):
+            self._screen_out = {}
+        self._screen_out[int(slot)] = (out, screen)   # (the library writes the one and reads the other until the batch's wait returns)
+        return out
+
+    def read_screen_withdraw(self, slot):
+        """rc_read_screen_into(out = NULL): the next batch of `slot` is not screened after all"""
+        self._ck(self._L.rc_read_screen_into(self._h, int(slot), None, 1, None))
 
     # ---- duplicate census: exact copies among the reads / pairs, before and after correction ----
     def dup_census_begin(self):

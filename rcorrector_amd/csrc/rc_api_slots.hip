@@ -16,23 +16,28 @@ template <class Entry>
 static int in_slot_lane(rc_ctx *c, int slot, bool submit, Entry entry)
 {
     if (!c || slot < 0 || slot >= RC_MAX_SLOTS) return RC_ERR_ARG;
-    // a submit takes the slot's registrations (rc_weak_profile_into, rc_read_depth_into) with it, whatever becomes of the submit
+    // a submit takes the slot's registrations (rc_weak_profile_into, rc_read_depth_into, rc_read_screen_into) with it, whatever
+    // becomes of the submit
     rc_ctx::rc_weak_reg weak;
     rc_ctx::rc_depth_reg depth;
+    rc_ctx::rc_screen_reg screen;
     if (submit) {
         std::swap(weak, c->weak_reg[slot]);
         std::swap(depth, c->depth_reg[slot]);
+        std::swap(screen, c->screen_reg[slot]);
     }
     rc_ctx *ln = rc_slot_lane(c, slot, submit, submit);
     if (!ln) return RC_ERR_HIP;
     if (submit) {
         ln->weak_cur = weak;
         ln->depth_cur = depth;
+        ln->screen_cur = screen;
     }
     const int rc = entry(static_cast<rc_ctx_full *>(ln), ln == c ? slot : 0);
     if (submit) {  // (a submit that returned in front of slot_download: nothing stays behind)
         ln->weak_cur = rc_ctx::rc_weak_reg();
         ln->depth_cur = rc_ctx::rc_depth_reg();
+        ln->screen_cur = rc_ctx::rc_screen_reg();
     }
     if (rc && ln != c) rc_lane_error(c, ln);
     return rc;
@@ -48,7 +53,7 @@ static int slot_acquire(rc_ctx_full *ctx, int slot, const char *name, const char
         rc_set_error(ctx, "%s: slot %d still holds a batch (%s first)", name, slot, wait_hint);
         return RC_ERR_STATE;
     }
-    sl.weak.out = sl.depth.out = nullptr;  // (slot_download sets them for a batch that has the registration)
+    sl.weak.out = sl.depth.out = sl.screen.out = nullptr;  // (slot_download sets them for a batch that has the registration)
     sl.obs.reset();         // (rc_correct_observed stages into it what the armed observers take of the batch)
     *out = &sl;
     return RC_OK;
@@ -165,7 +170,8 @@ static void payload_back(const rc_slot_payload &pl, size_t total)
 // sl.out or the slot's staging.  one_copy: where the caller's four arrays are one block, as the device's are, one copy instead
 // of four.  A batch submitted with a weak-profile registration (rc_weak_profile_into: ctx->weak_cur) has its corrected arena
 // profiled first, behind its last kernel on its own stream, and the 16 bytes per read come down with the results; one with a
-// depth registration (rc_read_depth_into: ctx->depth_cur) has its k-mer depth taken the same way.
+// depth registration (rc_read_depth_into: ctx->depth_cur) has its k-mer depth taken the same way, one with a screen
+// registration (rc_read_screen_into: ctx->screen_cur) its hit profile against the registered context's table.
 template <class First>
 static int slot_download(rc_ctx_full *ctx, rc_slot &sl, bool one_copy, First first)
 {
@@ -174,9 +180,11 @@ static int slot_download(rc_ctx_full *ctx, rc_slot &sl, bool one_copy, First fir
     const int32_t *d_res = (const int32_t *)sl.d_res.p;
     const rc_ctx::rc_weak_reg weak = ctx->weak_cur;
     const rc_ctx::rc_depth_reg depth = ctx->depth_cur;
+    const rc_ctx::rc_screen_reg screen = ctx->screen_cur;
     ctx->weak_cur = rc_ctx::rc_weak_reg();
     ctx->depth_cur = rc_ctx::rc_depth_reg();
-    sl.depth.out = nullptr;
+    ctx->screen_cur = rc_ctx::rc_screen_reg();
+    sl.depth.out = sl.screen.out = nullptr;
     int prc;
     if ((prc = payload_reserve(ctx, sl.weak, weak.out, total))) return prc;
     if (sl.weak.out && (prc = rc_launch_weak_profile(ctx, (const uint8_t *)sl.d_seq.p, sl.arena_bytes, (const uint32_t *)sl.d_off.p, (uint32_t)total,
@@ -185,11 +193,16 @@ static int slot_download(rc_ctx_full *ctx, rc_slot &sl, bool one_copy, First fir
     if ((prc = payload_reserve(ctx, sl.depth, depth.out, total))) return prc;
     if (sl.depth.out && (prc = rc_launch_read_depth(ctx, (const uint8_t *)sl.d_seq.p, sl.arena_bytes, (const uint32_t *)sl.d_off.p, (uint32_t)total, sl.depth.d.p)))
         return prc;
+    if ((prc = payload_reserve(ctx, sl.screen, screen.out, total))) return prc;
+    if (sl.screen.out && (prc = rc_launch_read_screen(ctx, screen.screen, (const uint8_t *)sl.d_seq.p, sl.arena_bytes, (const uint32_t *)sl.d_off.p,
+                                                      (uint32_t)total, screen.min_count, sl.screen.d.p)))
+        return prc;
     RC_CHECK_HIP(ctx, hipEventRecord(sl.e_k, ctx->stream));
     RC_CHECK_HIP(ctx, hipStreamWaitEvent(ctx->s_d2h, sl.e_k, 0));
     if (const int rc = first()) return rc;
     if ((prc = payload_download(ctx, sl.weak, total))) return prc;
     if ((prc = payload_download(ctx, sl.depth, total))) return prc;
+    if ((prc = payload_download(ctx, sl.screen, total))) return prc;
     if (!sl.res_pinned) {
         RC_CHECK_HIP(ctx, hipMemcpyAsync(sl.p_res.p, d_res, total * 16, hipMemcpyDeviceToHost, ctx->s_d2h));
     } else if (one_copy && o.l == o.ret + total && o.m == o.l + total && o.h == o.m + total) {
@@ -210,6 +223,7 @@ static void slot_results_back(const rc_slot &sl)
     const size_t total = sl.total_reads;
     payload_back(sl.weak, total);
     payload_back(sl.depth, total);
+    payload_back(sl.screen, total);
     if (sl.res_pinned) return;
     const int32_t *r = (const int32_t *)sl.p_res.p;
     memcpy(sl.out.ret, r, total * 4);

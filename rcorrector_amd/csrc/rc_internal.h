@@ -115,7 +115,7 @@ struct rc_kernel_timer {
     uint64_t launches = 0;
 };
 
-enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_TRUST_PLANES = 5, RC_T_TRUST = 6, RC_T_DEPTH = 7, RC_T_COUNT };
+enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_TRUST_PLANES = 5, RC_T_TRUST = 6, RC_T_DEPTH = 7, RC_T_SCREEN = 8, RC_T_COUNT };
 
 // what describes a k-mer table in HBM: a context that shares or copies another's table, or a slot lane its parent's, takes all of it
 // in one assignment, and rc_view reads nothing else (but k)
@@ -218,6 +218,15 @@ struct rc_ctx : rc_table_desc {
         void *out = nullptr;  // rc_read_depth[total]
     };
     rc_depth_reg depth_reg[4], depth_cur;
+    // hit profile against a second k-mer set (rc_read_screen_device / rc_read_screen_into; kernel in rc_screen.hip): the
+    // registrations travel the same way; `screen` is the context whose table the batch's reads are looked up in -- the caller
+    // keeps it and its table alive until the batch's wait
+    struct rc_screen_reg {
+        void *out = nullptr;  // rc_read_screen[total]
+        const rc_ctx *screen = nullptr;
+        int32_t min_count = 1;
+    };
+    rc_screen_reg screen_reg[4], screen_cur;
     // duplicate census (rc_dup_census_begin; kernels in rc_dups.hip).  In the context it was opened on (the batches of its slot
     // lanes add to it too: rc_home): the keys of every unit seen, version 0 = before and 1 = after correction, 16 bytes per
     // unit each, dup_n units of dup_cap; dup_gen counts the begins (keys a batch staged for one census never reach the next).
@@ -418,6 +427,11 @@ int rc_launch_weak_profile(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, con
 // rc_depth.hip: d_out[r] = the rc_read_depth of read r, one launch; a read whose offsets leave the arena, or of more than
 // RC_MAX_READ_LENGTH - 1 bases, gets four zeros
 int rc_launch_read_depth(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, void *d_out);
+
+// rc_screen.hip: d_out[r] = the rc_read_screen of read r against `screen`'s table (same k, same device: checked), one launch on
+// ctx's stream; the reads that are none get four zeros, as above
+int rc_launch_read_screen(rc_ctx *ctx, const rc_ctx *screen, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int min_count,
+                          void *d_out);
 
 // rc_weak.hip: the two bit planes alone (what rc_launch_weak_profile launches first): *solid / *weak point into `planes`,
 // *lead = the bytes between the 16-byte boundary the planes start at and d_seq.  rc_trust.hip: the planes of the arena at
