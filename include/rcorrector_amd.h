@@ -851,6 +851,31 @@ int rc_selftest_get_bound(rc_ctx *ctx, const int32_t *c, size_t n, double error_
  * read of more than 160 bases), without classification or without candidates, or n is not its number of reads. */
 int rc_debug_routes(rc_ctx *ctx, uint8_t *cls_out, uint8_t *cand_out, uint64_t *runs_out, uint32_t n);
 
+/* test support: the device side of the packed boundary alone (rc_submit_packed / rc_wait_packed without a correction), through
+ * the launchers the transports use; needs no table and no run parameters.  All pointers are host memory.  Runs, on the context's
+ * stream: the expansion of `packed` ((nbytes + 15) / 16 words, rc_pack_bases), the NULs of the n_reads reads of `off` (n_reads + 1
+ * offsets over the arena's nbytes bytes) and the n_exc exceptions into a device arena of round16(nbytes) + RC_SELFTEST_ARENA_SLACK
+ * bytes that held RC_SELFTEST_CANARY in every byte -- all of it comes back in unpacked_out --; then, with the arena's first nbytes
+ * bytes replaced by `after` (what a correction would have left; the padding stays as expanded), the fix list against the packed
+ * codes and the exceptions with room for `cap` entries, into device arrays of cap + RC_SELFTEST_FIX_SLACK entries that held the
+ * canary in every byte: *n_fix_out = the number of fixes (all of them, as rc_packed_batch.n_fix), fix_pos_out / fix_chr_out = the
+ * arrays with their slack.  Waits for the stream.  RC_ERR_ARG for null or inconsistent arguments: offsets that do not ascend from 0
+ * to nbytes, an exception outside the arena. */
+#define RC_SELFTEST_CANARY 0xA5
+#define RC_SELFTEST_ARENA_SLACK 64
+#define RC_SELFTEST_FIX_SLACK 64
+int rc_selftest_transport_packed(rc_ctx *ctx, const uint32_t *packed, size_t nbytes, const uint32_t *off, uint32_t n_reads, const uint32_t *exc_pos,
+                                 const uint8_t *exc_chr, uint32_t n_exc, const uint8_t *after, uint8_t *unpacked_out, uint32_t *n_fix_out, uint32_t cap,
+                                 uint32_t *fix_pos_out, uint8_t *fix_chr_out);
+/* test support: the fix list of the resident boundary alone (rc_submit_resident's byte comparison), through the transport's
+ * launcher.  orig_a: shift_a + na + RC_SELFTEST_ARENA_SLACK host bytes that go to a 16-byte aligned device address as they are --
+ * shift_a (0..15) bytes in front, the na uncorrected bytes of the first range, the slack a kept arena carries behind them; orig_b
+ * likewise for the second range (NULL where nb == 0).  after: the na + nb bytes of the corrected arena, placed at an aligned
+ * address.  n_fix_out, cap, fix_pos_out and fix_chr_out as above.  Waits for the stream; RC_ERR_ARG for null arguments, a shift
+ * above 15 or 4 GiB and more. */
+int rc_selftest_transport_bytes(rc_ctx *ctx, const uint8_t *orig_a, size_t na, uint32_t shift_a, const uint8_t *orig_b, size_t nb, uint32_t shift_b,
+                                const uint8_t *after, uint32_t *n_fix_out, uint32_t cap, uint32_t *fix_pos_out, uint8_t *fix_chr_out);
+
 /* summary counters, struct _summary main.cpp:32-36,73-79: reads and corrected bases of every batch
  * this context has corrected through any entry point (accumulated on the device; waits for the
  * context's kernels) */

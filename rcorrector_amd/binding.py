@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
     "rc_pack_bases", "rc_submit_packed", "rc_wait_packed", "rc_apply_fixes",
     "rc_profile_enable", "rc_profile_get", "rc_profile_reset", "rc_profile_correct_counters", "rc_profile_read_rounds", "rc_selftest_get_bound", "rc_debug_routes", "rc_summary",
+    "rc_selftest_transport_packed", "rc_selftest_transport_bytes",
 ]
 
 
@@ -115,6 +116,10 @@ class _RecurCensus(C.Structure):
 
 
 RECUR_FLANK = 14
+
+SELFTEST_CANARY = 0xA5        # RC_SELFTEST_CANARY
+SELFTEST_ARENA_SLACK = 64     # RC_SELFTEST_ARENA_SLACK
+SELFTEST_FIX_SLACK = 64       # RC_SELFTEST_FIX_SLACK
 
 
 def recur_key_decode(key):
@@ -310,6 +315,8 @@ def load_library():
     L.rc_profile_read_rounds.argtypes = [vp, vp]
     L.rc_selftest_get_bound.argtypes = [vp, vp, sz, C.c_double, vp, vp]
     L.rc_debug_routes.argtypes = [vp, vp, vp, vp, C.c_uint32]
+    L.rc_selftest_transport_packed.argtypes = [vp, vp, sz, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp]
+    L.rc_selftest_transport_bytes.argtypes = [vp, vp, sz, C.c_uint32, vp, sz, C.c_uint32, vp, vp, C.c_uint32, vp, vp]
     L.rc_summary.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
@@ -1043,6 +1050,42 @@ class Context:
         cls, cand, runs = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint64)
         self._ck(self._L.rc_debug_routes(self._h, cls.ctypes.data, cand.ctypes.data, runs.ctypes.data, n))
         return cls, cand, runs
+
+    def selftest_transport_packed(self, packed, nbytes, off, exc_pos, exc_chr, after, cap):
+        """Test support (rc_selftest_transport_packed): the packed boundary's kernels alone.  Returns (unpacked, n_fix, fix_pos,
+        fix_chr): the whole device arena after the expansion (round16(nbytes) + SELFTEST_ARENA_SLACK bytes, SELFTEST_CANARY where
+        nothing was written), the number of fixes between the packed codes and `after`, and the fix arrays of cap +
+        SELFTEST_FIX_SLACK entries (canary bytes where nothing was written)."""
+        packed, off = np.ascontiguousarray(packed, dtype=np.uint32), np.ascontiguousarray(off, dtype=np.uint32)
+        exc_pos, exc_chr = np.ascontiguousarray(exc_pos, dtype=np.uint32), np.ascontiguousarray(exc_chr, dtype=np.uint8)
+        after = np.ascontiguousarray(after, dtype=np.uint8)
+        nbytes, cap = int(nbytes), int(cap)
+        if len(packed) != (nbytes + 15) // 16 or len(after) != nbytes or len(exc_pos) != len(exc_chr) or len(off) < 1:
+            raise ValueError("selftest_transport_packed: the arrays do not describe an arena of %d bytes" % nbytes)
+        unpacked = np.zeros((nbytes + 15) // 16 * 16 + SELFTEST_ARENA_SLACK, np.uint8)
+        n_fix = np.zeros(1, np.uint32)
+        fix_pos, fix_chr = np.zeros(cap + SELFTEST_FIX_SLACK, np.uint32), np.zeros(cap + SELFTEST_FIX_SLACK, np.uint8)
+        self._ck(self._L.rc_selftest_transport_packed(self._h, packed.ctypes.data, nbytes, off.ctypes.data, len(off) - 1, exc_pos.ctypes.data,
+                                                      exc_chr.ctypes.data, len(exc_pos), after.ctypes.data, unpacked.ctypes.data,
+                                                      n_fix.ctypes.data, cap, fix_pos.ctypes.data, fix_chr.ctypes.data))
+        return unpacked, int(n_fix[0]), fix_pos, fix_chr
+
+    def selftest_transport_bytes(self, orig_a, na, shift_a, orig_b, nb, shift_b, after, cap):
+        """Test support (rc_selftest_transport_bytes): the resident boundary's fix list alone.  orig_a / orig_b: shift + n +
+        SELFTEST_ARENA_SLACK bytes each (what lies in front of a range down to the 16-byte boundary, the range, the slack behind
+        it; orig_b None where nb == 0), after: the na + nb corrected bytes.  Returns (n_fix, fix_pos, fix_chr) as above."""
+        na, nb, shift_a, shift_b, cap = int(na), int(nb), int(shift_a), int(shift_b), int(cap)
+        orig_a = np.ascontiguousarray(orig_a, dtype=np.uint8)
+        orig_b = None if orig_b is None else np.ascontiguousarray(orig_b, dtype=np.uint8)
+        after = np.ascontiguousarray(after, dtype=np.uint8)
+        if len(orig_a) != shift_a + na + SELFTEST_ARENA_SLACK or len(after) != na + nb or (orig_b is None) != (nb == 0) or \
+                (orig_b is not None and len(orig_b) != shift_b + nb + SELFTEST_ARENA_SLACK):
+            raise ValueError("selftest_transport_bytes: the arrays do not describe ranges of %d and %d bytes" % (na, nb))
+        n_fix = np.zeros(1, np.uint32)
+        fix_pos, fix_chr = np.zeros(cap + SELFTEST_FIX_SLACK, np.uint32), np.zeros(cap + SELFTEST_FIX_SLACK, np.uint8)
+        self._ck(self._L.rc_selftest_transport_bytes(self._h, orig_a.ctypes.data, na, shift_a, None if orig_b is None else orig_b.ctypes.data, nb,
+                                                     shift_b, after.ctypes.data, n_fix.ctypes.data, cap, fix_pos.ctypes.data, fix_chr.ctypes.data))
+        return int(n_fix[0]), fix_pos, fix_chr
 
     def summary(self):
         a, b = C.c_uint64(0), C.c_uint64(0)

@@ -456,6 +456,105 @@ int rc_selftest_get_bound(rc_ctx *ctx, const int32_t *c, size_t n, double error_
     return RC_OK;
 }
 
+}  // extern "C"
+
+// test support: the fix list of a launch into device arrays of cap + RC_SELFTEST_FIX_SLACK entries that held the canary, and what
+// came of it into the caller's arrays (the count, the arrays with their slack).  `launch` gets d_n_fix, d_fix_pos, d_fix_chr.
+template <class Launch>
+static int selftest_fix_list(rc_ctx *ctx, uint32_t cap, uint32_t *n_fix_out, uint32_t *fix_pos_out, uint8_t *fix_chr_out, Launch launch)
+{
+    const size_t room = (size_t)cap + RC_SELFTEST_FIX_SLACK;
+    rc_dev_tmp b_n, b_pos, b_chr;
+    RC_CHECK_HIP(ctx, b_n.alloc(64));
+    RC_CHECK_HIP(ctx, b_pos.alloc(room * 4));
+    RC_CHECK_HIP(ctx, b_chr.alloc(room));
+    RC_CHECK_HIP(ctx, hipMemsetAsync(b_pos.p, RC_SELFTEST_CANARY, room * 4, ctx->stream));
+    RC_CHECK_HIP(ctx, hipMemsetAsync(b_chr.p, RC_SELFTEST_CANARY, room, ctx->stream));
+    if (const int rc = launch(b_n.as<uint32_t>(), b_pos.as<uint32_t>(), b_chr.as<uint8_t>())) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    RC_CHECK_HIP(ctx, hipMemcpyAsync(n_fix_out, b_n.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    RC_CHECK_HIP(ctx, hipMemcpyAsync(fix_pos_out, b_pos.p, room * 4, hipMemcpyDeviceToHost, ctx->stream));
+    RC_CHECK_HIP(ctx, hipMemcpyAsync(fix_chr_out, b_chr.p, room, hipMemcpyDeviceToHost, ctx->stream));
+    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RC_OK;
+}
+
+extern "C" {
+
+// test support: the packed boundary's device side alone (rc_transport.hip through its production launchers) -- no table, no run
+// parameters, no correction: `after` stands for the arena the correction kernels would have left.
+int rc_selftest_transport_packed(rc_ctx *ctx, const uint32_t *packed, size_t nbytes, const uint32_t *off, uint32_t n_reads, const uint32_t *exc_pos,
+                                 const uint8_t *exc_chr, uint32_t n_exc, const uint8_t *after, uint8_t *unpacked_out, uint32_t *n_fix_out, uint32_t cap,
+                                 uint32_t *fix_pos_out, uint8_t *fix_chr_out)
+{
+    if (!ctx || !unpacked_out || !n_fix_out || !fix_pos_out || !fix_chr_out || nbytes >= (1ull << 32) || (size_t)cap + RC_SELFTEST_FIX_SLACK >= (1ull << 32) ||
+        (nbytes && (!packed || !after)) || (n_reads && !off) || (n_exc && (!exc_pos || !exc_chr)))
+        return RC_ERR_ARG;
+    // (the terminator and exception kernels write seq[off[i+1]-1] and seq[exc_pos[i]] unchecked: what rc_submit_packed refuses)
+    if (n_reads && (off[0] != 0 || off[n_reads] != nbytes)) return RC_ERR_ARG;
+    for (uint32_t i = 0; i < n_reads; ++i)
+        if (off[i + 1] <= off[i]) return RC_ERR_ARG;
+    for (uint32_t i = 0; i < n_exc; ++i)
+        if (exc_pos[i] >= nbytes) return RC_ERR_ARG;
+    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n_words = (nbytes + 15) / 16, arena = n_words * 16 + RC_SELFTEST_ARENA_SLACK;  // (d_seq of submit_packed)
+    rc_dev_tmp b_packed, b_seq, b_off, b_epos, b_echr;
+    RC_CHECK_HIP(ctx, b_packed.alloc(n_words * 4 + 64));
+    RC_CHECK_HIP(ctx, b_seq.alloc(arena));
+    RC_CHECK_HIP(ctx, b_off.alloc(((size_t)n_reads + 1) * 4));
+    RC_CHECK_HIP(ctx, b_epos.alloc((size_t)n_exc * 4));
+    RC_CHECK_HIP(ctx, b_echr.alloc(n_exc));
+    RC_CHECK_HIP(ctx, hipMemsetAsync(b_seq.p, RC_SELFTEST_CANARY, arena, ctx->stream));
+    if (n_words) RC_CHECK_HIP(ctx, hipMemcpyAsync(b_packed.p, packed, n_words * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (n_reads) RC_CHECK_HIP(ctx, hipMemcpyAsync(b_off.p, off, ((size_t)n_reads + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (n_exc) {
+        RC_CHECK_HIP(ctx, hipMemcpyAsync(b_epos.p, exc_pos, (size_t)n_exc * 4, hipMemcpyHostToDevice, ctx->stream));
+        RC_CHECK_HIP(ctx, hipMemcpyAsync(b_echr.p, exc_chr, n_exc, hipMemcpyHostToDevice, ctx->stream));
+    }
+    int rc = rc_launch_unpack(ctx, b_packed.as<uint32_t>(), nbytes, b_off.as<uint32_t>(), n_reads, b_epos.as<uint32_t>(), b_echr.as<uint8_t>(), n_exc,
+                              b_seq.as<uint8_t>());
+    if (rc) {
+        (void)hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
+    RC_CHECK_HIP(ctx, hipMemcpyAsync(unpacked_out, b_seq.p, arena, hipMemcpyDeviceToHost, ctx->stream));
+    // the corrected bytes; the padding behind them stays as the unpack left it
+    if (nbytes) RC_CHECK_HIP(ctx, hipMemcpyAsync(b_seq.p, after, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    rc = selftest_fix_list(ctx, cap, n_fix_out, fix_pos_out, fix_chr_out, [&](uint32_t *d_n, uint32_t *d_pos, uint8_t *d_chr) {
+        return rc_launch_fix_list(ctx, b_packed.as<uint32_t>(), nbytes, b_seq.as<uint8_t>(), b_epos.as<uint32_t>(), n_exc, d_n, cap, d_pos, d_chr);
+    });
+    (void)hipStreamSynchronize(ctx->stream);  // (the uploads read the caller's arrays until here, whatever became of the launches)
+    return rc;
+}
+
+// test support: k_fix_list_bytes alone, the uncorrected bytes at any alignment (the ranges of kept arenas a resident batch names)
+int rc_selftest_transport_bytes(rc_ctx *ctx, const uint8_t *orig_a, size_t na, uint32_t shift_a, const uint8_t *orig_b, size_t nb, uint32_t shift_b,
+                                const uint8_t *after, uint32_t *n_fix_out, uint32_t cap, uint32_t *fix_pos_out, uint8_t *fix_chr_out)
+{
+    if (!ctx || !n_fix_out || !fix_pos_out || !fix_chr_out || shift_a > 15 || shift_b > 15 || na >= (1ull << 32) || nb >= (1ull << 32) ||
+        na + nb >= (1ull << 32) || (size_t)cap + RC_SELFTEST_FIX_SLACK >= (1ull << 32) || (na && !orig_a) || (nb && !orig_b) || (na + nb && !after))
+        return RC_ERR_ARG;
+    RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t nbytes = na + nb, arena = ((nbytes + 15) & ~(size_t)15) + RC_SELFTEST_ARENA_SLACK;  // (d_seq of submit_resident)
+    const size_t span_a = shift_a + na + RC_SELFTEST_ARENA_SLACK, span_b = shift_b + nb + RC_SELFTEST_ARENA_SLACK;
+    rc_dev_tmp b_a, b_b, b_seq;
+    RC_CHECK_HIP(ctx, b_a.alloc(span_a + 16));  // (hipMalloc aligns to 256 bytes; whole 16-byte words behind the slack)
+    RC_CHECK_HIP(ctx, b_b.alloc(span_b + 16));
+    RC_CHECK_HIP(ctx, b_seq.alloc(arena));
+    RC_CHECK_HIP(ctx, hipMemsetAsync(b_seq.p, RC_SELFTEST_CANARY, arena, ctx->stream));
+    if (orig_a) RC_CHECK_HIP(ctx, hipMemcpyAsync(b_a.p, orig_a, span_a, hipMemcpyHostToDevice, ctx->stream));
+    if (orig_b) RC_CHECK_HIP(ctx, hipMemcpyAsync(b_b.p, orig_b, span_b, hipMemcpyHostToDevice, ctx->stream));
+    if (nbytes) RC_CHECK_HIP(ctx, hipMemcpyAsync(b_seq.p, after, nbytes, hipMemcpyHostToDevice, ctx->stream));
+    const int rc = selftest_fix_list(ctx, cap, n_fix_out, fix_pos_out, fix_chr_out, [&](uint32_t *d_n, uint32_t *d_pos, uint8_t *d_chr) {
+        return rc_launch_fix_list_bytes(ctx, b_a.as<uint8_t>() + shift_a, na, nb ? b_b.as<uint8_t>() + shift_b : nullptr, nb, b_seq.as<uint8_t>(), d_n, cap,
+                                        d_pos, d_chr);
+    });
+    (void)hipStreamSynchronize(ctx->stream);
+    return rc;
+}
+
 // test support: which kernel finished each read of the batch this context ran last -- cls (0: finished before k_correct; k_single
 // clears it, rc_single.h), cand (the threshold kernel's flag for k_single: the number of stretches) and runs (the stretches, x in
 // the low word) as they lie in HBM.  Copies only: no kernel is launched, and the correction kernels know nothing of it.
