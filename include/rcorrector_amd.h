@@ -356,6 +356,37 @@ int rc_read_screen_device(rc_ctx *ctx, const rc_ctx *screen, const uint8_t *d_se
  * RC_STATUS_STATE: no table in `screen`. */
 int rc_read_screen_into(rc_ctx *ctx, int slot, const rc_ctx *screen, int32_t min_count, rc_read_screen *out);
 
+/* ---- normalisation by k-mer depth: which reads or pairs to keep so that no transcript is covered much beyond a target ---------
+ * What an assembler does first with corrected reads (in-silico normalisation): count the k-mers, take every read's median k-mer
+ * coverage, keep a unit with probability target / median.  The counter and rc_read_depth are the two expensive stages; this is
+ * the selection.  The scheme is after Trinity's normalisation with --pairs_together -- the mates' medians averaged, a unit kept
+ * with max_cov / median -- but neither its random stream nor byte parity with it is claimed, and its coefficient-of-variation
+ * filter has no counterpart.  A UNIT is a read (mode 0), read u with read n_units + u (mode 1) or reads 2u and 2u + 1 (mode 2):
+ * the duplicate census's modes.
+ *   depth D   of the rc_read_depth of the unit's mates, those with valid > 0 only: one such mate -- its median; two --
+ *             (m1 + m2 + 1) >> 1, unsigned; none -- the unit is NOVALID
+ *   draw r    z = seed + (index + 1) * 0x9E3779B97F4A7C15 through the splitmix64 finaliser (z ^= z >> 30, z *= 0xBF58476D1CE4E5B9,
+ *             z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31), r its upper 32 bits; index = unit_base + u, 64 bits: the
+ *             unit's number in the WHOLE input, not in the batch
+ *   outcome   RC_NORM_NOVALID: no mate with valid > 0; else RC_NORM_LOW: D < min_cov; else RC_NORM_KEPT: D <= target or
+ *             (uint64_t)r * D < (uint64_t)target << 32; else RC_NORM_OVER
+ * A unit is kept with probability min(1, target / D) to within 2^-32, and the decision depends on (seed, index, D) alone: a run
+ * is reproducible and the same however the input is cut into batches.  Integer arithmetic throughout (rc_norm.h).  No reference
+ * counterpart. */
+#define RC_NORM_OVER 0
+#define RC_NORM_KEPT 1
+#define RC_NORM_LOW 2
+#define RC_NORM_NOVALID 3
+/* d_depth: what rc_read_depth_device left in HBM, n_units entries in mode 0 and 2 * n_units in modes 1 and 2, on a 16-byte
+ * boundary.  d_keep[u] = the outcome of unit u for u < n_units; no other byte is written.  d_tally: 4 + 2 * (max_bin + 1) words
+ * in HBM that the call ADDS to -- it accumulates over batches, the caller zeroes it: the four outcome counts indexed by outcome
+ * value, then before[min(D, max_bin)] over the units that are not NOVALID, then after[min(D, max_bin)] over the KEPT ones.
+ * Asynchronous on the context's stream (rc_sync() to wait); ctx needs no table.  n_units == 0: RC_STATUS_OK, no launch.
+ * RC_STATUS_ARG (checked whatever n_units is): a mode outside 0..2, target == 0 or >= 2^31, max_bin outside 1 .. 65535; with
+ * n_units > 0: a null pointer, a misaligned d_depth or d_tally.  rc_profile_get's kernel 9 times it. */
+int rc_norm_select_device(rc_ctx *ctx, const rc_read_depth *d_depth, uint32_t n_units, int mode, uint64_t unit_base, uint32_t target,
+                          uint32_t min_cov, uint64_t seed, uint32_t max_bin, uint8_t *d_keep, uint64_t *d_tally);
+
 /* ---- duplicate census: how many reads / pairs are exact copies of one another, before and after correction ------------------
  * A UNIT is a read (mode 0) or a pair (mode 1: read r of the first half and read r of the second; mode 2: reads 2u and 2u + 1 --
  * the mates of the correction report).  Two units are duplicates when their base strings are byte for byte equal: equal
@@ -830,8 +861,8 @@ int rc_profile_correct_counters(rc_ctx *ctx, uint64_t *reads_listed, uint64_t *g
  * (MAX_TRIAL, ErrorCorrection.cpp:7; the straggler of tools/find_straggler.py).  NULL switches it off. */
 int rc_profile_read_rounds(rc_ctx *ctx, int32_t *d_rounds);
 /* kernel 0 = probe, 1 = threshold, 2 = correct, 3 = isolated substitutions, 4 = weak-k-mer profile, 5 = the trust profile's
- * planes, 6 = its accumulate and column sums, 7 = per-read k-mer depth, 8 = per-read screen against a second k-mer set;
- * accumulated since the last reset */
+ * planes, 6 = its accumulate and column sums, 7 = per-read k-mer depth, 8 = per-read screen against a second k-mer set,
+ * 9 = normalisation's unit selection; accumulated since the last reset */
 int rc_profile_get(rc_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
 int rc_profile_reset(rc_ctx *ctx);
 

@@ -21,6 +21,7 @@ ABI_SYMBOLS = [
     "rc_weak_profile_device", "rc_weak_profile_into",
     "rc_read_depth_device", "rc_read_depth_into",
     "rc_read_screen_device", "rc_read_screen_into",
+    "rc_norm_select_device",
     "rc_dup_census_begin", "rc_dup_census_get", "rc_dup_census_end", "rc_read_keys_device", "rc_dup_census_merge",
     "rc_recur_census_begin", "rc_recur_census_get", "rc_recur_census_end", "rc_recur_census_merge", "rc_change_keys_device",
     "rc_trust_profile_device", "rc_trust_profile_begin", "rc_trust_profile_get", "rc_trust_profile_end",
@@ -265,6 +266,7 @@ def load_library():
     L.rc_read_depth_into.argtypes = [vp, C.c_int, vp]
     L.rc_read_screen_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, vp]
     L.rc_read_screen_into.argtypes = [vp, C.c_int, vp, C.c_int32, vp]
+    L.rc_norm_select_device.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, vp, vp]
     L.rc_dup_census_begin.argtypes = [vp]
     L.rc_dup_census_get.argtypes = [vp, C.c_uint32, C.POINTER(_DupCensus)]
     L.rc_dup_census_end.argtypes = [vp]
@@ -615,6 +617,15 @@ class Context:
     def read_depth_withdraw(self, slot):
         """rc_read_depth_into(out = NULL): the next batch of `slot` has its depth not taken after all"""
         self._ck(self._L.rc_read_depth_into(self._h, int(slot), None))
+
+    # ---- normalisation by k-mer depth: one byte per unit from the depths of its mates ----
+    def norm_select_device(self, d_depth, n_units, mode, unit_base, target, min_cov, seed, max_bin, d_keep, d_tally):
+        """rc_norm_select_device: d_depth: what read_depth_device left in HBM (n_units rows in mode 0, 2 * n_units in modes 1
+        and 2); d_keep: device memory for n_units bytes (0 over, 1 kept, 2 low, 3 no valid window: RC_NORM_*); the outcomes and the
+        unit depths are ADDED to d_tally: device memory for 4 + 2 * (max_bin + 1) uint64, zeroed by the caller.  unit_base: the
+        units of the whole input in front of this batch.  Needs no table.  Asynchronous: sync() to wait."""
+        self._ck(self._L.rc_norm_select_device(self._h, _ptr(d_depth), int(n_units), int(mode), int(unit_base), int(target), int(min_cov), int(seed),
+                                               int(max_bin), _ptr(d_keep), _ptr(d_tally)))
 
     # ---- per-read screen against a second k-mer set: valid and hit windows, covered bases, longest run of hits ----
     def read_screen_device(self, screen, d_seq, d_off, n_reads, nbytes, max_read_len, d_out, min_count=1):

@@ -115,7 +115,7 @@ struct rc_kernel_timer {
     uint64_t launches = 0;
 };
 
-enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_TRUST_PLANES = 5, RC_T_TRUST = 6, RC_T_DEPTH = 7, RC_T_SCREEN = 8, RC_T_COUNT };
+enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_TRUST_PLANES = 5, RC_T_TRUST = 6, RC_T_DEPTH = 7, RC_T_SCREEN = 8, RC_T_NORM = 9, RC_T_COUNT };
 
 // what describes a k-mer table in HBM: a context that shares or copies another's table, or a slot lane its parent's, takes all of it
 // in one assignment, and rc_view reads nothing else (but k)
@@ -432,6 +432,11 @@ int rc_launch_read_depth(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const
 // ctx's stream; the reads that are none get four zeros, as above
 int rc_launch_read_screen(rc_ctx *ctx, const rc_ctx *screen, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int min_count,
                           void *d_out);
+
+// rc_norm.hip: d_keep[u] = the outcome of unit u (rc_norm.h) from the rc_read_depth of its mates, the outcomes and the unit depths
+// added to d_tally (4 + 2 (max_bin + 1) uint64 in HBM); one launch, no table
+int rc_launch_norm_select(rc_ctx *ctx, const void *d_depth, uint32_t n_units, int mode, uint64_t unit_base, uint32_t target, uint32_t min_cov, uint64_t seed,
+                          uint32_t max_bin, uint8_t *d_keep, uint64_t *d_tally);
 
 // rc_weak.hip: the two bit planes alone (what rc_launch_weak_profile launches first): *solid / *weak point into `planes`,
 // *lead = the bytes between the 16-byte boundary the planes start at and d_seq.  rc_trust.hip: the planes of the arena at

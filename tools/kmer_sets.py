@@ -1,4 +1,4 @@
-"""What the tools that put a k-mer set into a Context have in common (kmer_compare, read_screen): sequence files read in
+"""What the tools that put a k-mer set into a Context have in common (kmer_compare, read_screen, read_normalize): sequence files read in
 Python -- FASTA of any line length or FASTQ, plain or gzip -- cut into arenas for the GPU counter, and a set loaded from a
 k-mer dump or counted from such files."""
 import gzip
@@ -32,6 +32,39 @@ def read_records(path):
                 else:
                     parts.append(line.rstrip(b"\r\n"))
             yield name, b"".join(parts)
+        elif first.strip():
+            raise ValueError("%s: neither FASTA nor FASTQ (first line starts with %r)" % (path, first[:1]))
+
+
+def read_raw_records(path):
+    """(name, sequence, text) of every record, as read_records names and joins them; text is the record as a tool writes it
+    back: a FASTQ record's four lines byte for byte (a last line without a line end gets one), a FASTA record's header line
+    as it is and its sequence on one line"""
+    def name_of(header):
+        words = header[1:].split()
+        return words[0] if words else b""
+
+    def ended(line):
+        return line if line.endswith(b"\n") else line + b"\n"
+
+    with open(path, "rb") as f:
+        magic = f.read(2)
+    with (gzip.open(path, "rb") if magic == b"\x1f\x8b" else open(path, "rb")) as f:
+        first = f.readline()
+        if first.startswith(b"@"):
+            while first:
+                seq, plus, qual = f.readline(), f.readline(), f.readline()
+                yield name_of(first), seq.rstrip(b"\r\n"), first + seq + plus + ended(qual) if qual else ended(first + seq + plus)
+                first = f.readline()
+        elif first.startswith(b">"):
+            header, parts = first, []
+            for line in f:
+                if line.startswith(b">"):
+                    yield name_of(header), b"".join(parts), ended(header) + b"".join(parts) + b"\n"
+                    header, parts = line, []
+                else:
+                    parts.append(line.rstrip(b"\r\n"))
+            yield name_of(header), b"".join(parts), ended(header) + b"".join(parts) + b"\n"
         elif first.strip():
             raise ValueError("%s: neither FASTA nor FASTQ (first line starts with %r)" % (path, first[:1]))
 
