@@ -566,6 +566,20 @@ class Context:
         """rc_change_report_end: disarms the report and frees what it held."""
         self._ck(self._L.rc_change_report_end(self._h))
 
+    # ---- the per-read payloads' one-shot registrations (weak_profile_into, read_depth_into, read_screen_into) ----
+    def _payload_into(self, kind, slot, total_reads, out, register, *also_held):
+        """The (total_reads, 4) int32 array of a payload registration: `out` checked, or a page-locked one allocated; handed
+        to register(address), then held under (kind, slot) with also_held (the library writes / reads them until the batch's
+        wait returns)."""
+        total_reads = int(total_reads)
+        if out is None:
+            out = self.host_array(total_reads * 4, dtype=np.int32).reshape(total_reads, 4)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.shape == (total_reads, 4)):
+            raise TypeError("out must be a C-contiguous int32 numpy array of shape (total_reads, 4)")
+        self._ck(register(out.ctypes.data))
+        self.__dict__.setdefault("_payload_out", {})[(kind, int(slot))] = (out,) + also_held
+        return out
+
     # ---- per-read weak-k-mer profile: weak windows, bad prefix / suffix, uncovered bases ----
     def weak_profile_device(self, d_seq, d_off, n_reads, nbytes, max_read_len, d_out, min_count=1):
         """rc_weak_profile_device: the reads of an arena in HBM as they are; d_out: device memory for n_reads x 4 int32
@@ -577,16 +591,7 @@ class Context:
         Returns a page-locked (total_reads, 4) int32 array -- columns weak, bad_prefix, bad_suffix, uncovered, rows indexed like
         ret / l / m / h -- that the batch's wait fills (out: a C-contiguous int32 array of that shape to fill instead, e.g. a
         pageable one).  One shot: every submit consumes the registration."""
-        total_reads = int(total_reads)
-        if out is None:
-            out = self.host_array(total_reads * 4, dtype=np.int32).reshape(total_reads, 4)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.shape == (total_reads, 4)):
-            raise TypeError("out must be a C-contiguous int32 numpy array of shape (total_reads, 4)")
-        self._ck(self._L.rc_weak_profile_into(self._h, int(slot), out.ctypes.data, int(min_count)))
-        if not hasattr(self, "_weak_out"):
-            self._weak_out = {}
-        self._weak_out[int(slot)] = out   # (the library writes it until the batch's wait returns)
-        return out
+        return self._payload_into("weak", slot, total_reads, out, lambda p: self._L.rc_weak_profile_into(self._h, int(slot), p, int(min_count)))
 
     def weak_profile_withdraw(self, slot):
         """rc_weak_profile_into(out = NULL): the next batch of `slot` is not profiled after all"""
@@ -603,16 +608,7 @@ class Context:
         corrected reads.  Returns a page-locked (total_reads, 4) int32 array -- columns valid, q1, median, q3, rows indexed like
         ret / l / m / h -- that the batch's wait fills (out: a C-contiguous int32 array of that shape to fill instead, e.g. a
         pageable one).  One shot: every submit consumes the registration."""
-        total_reads = int(total_reads)
-        if out is None:
-            out = self.host_array(total_reads * 4, dtype=np.int32).reshape(total_reads, 4)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.shape == (total_reads, 4)):
-            raise TypeError("out must be a C-contiguous int32 numpy array of shape (total_reads, 4)")
-        self._ck(self._L.rc_read_depth_into(self._h, int(slot), out.ctypes.data))
-        if not hasattr(self, "_depth_out"):
-            self._depth_out = {}
-        self._depth_out[int(slot)] = out   # (the library writes it until the batch's wait returns)
-        return out
+        return self._payload_into("depth", slot, total_reads, out, lambda p: self._L.rc_read_depth_into(self._h, int(slot), p))
 
     def read_depth_withdraw(self, slot):
         """rc_read_depth_into(out = NULL): the next batch of `slot` has its depth not taken after all"""
@@ -641,16 +637,8 @@ class Context:
         covered, longest, rows indexed like ret / l / m / h -- that the batch's wait fills (out: a C-contiguous int32 array of
         that shape to fill instead, e.g. a pageable one).  One shot: every submit consumes the registration.  `screen` must
         keep its table until that wait; this context holds on to it until the next registration of the slot."""
-        total_reads = int(total_reads)
-        if out is None:
-            out = self.host_array(total_reads * 4, dtype=np.int32).reshape(total_reads, 4)
-        elif not (isinstance(out, np.ndarray) and out.dtype == np.int32 and out.flags.c_contiguous and out.shape == (total_reads, 4)):
-            raise TypeError("out must be a C-contiguous int32 numpy array of shape (total_reads, 4)")
-        self._ck(self._L.rc_read_screen_into(self._h, int(slot), screen._h, int(min_count), out.ctypes.data))
-        if not hasattr(self, "_screen_out"):
-            self._screen_out = {}
-        self._screen_out[int(slot)] = (out, screen)   # (the library writes the one and reads the other until the batch's wait returns)
-        return out
+        return self._payload_into("screen", slot, total_reads, out,
+                                  lambda p: self._L.rc_read_screen_into(self._h, int(slot), screen._h, int(min_count), p), screen)
 
     def read_screen_withdraw(self, slot):
         """rc_read_screen_into(out = NULL): the next batch of `slot` is not screened after all"""

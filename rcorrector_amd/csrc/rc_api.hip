@@ -303,12 +303,16 @@ void rc_destroy(rc_ctx *c)
         for (int i = 0; i < RC_MAX_SLOTS; ++i) {
             rc_slot &sl = ctx->slots[i];
             if (sl.e_done) (void)hipEventSynchronize(sl.e_done);
-            rc_hbuf *hb[] = {&sl.p_seq, &sl.p_qual, &sl.p_off, &sl.p_res, &sl.p_in, &sl.p_fix, &sl.p_nfix, &sl.weak.p, &sl.depth.p, &sl.screen.p};
+            rc_hbuf *hb[] = {&sl.p_seq, &sl.p_qual, &sl.p_off, &sl.p_res, &sl.p_in, &sl.p_fix, &sl.p_nfix};
             for (rc_hbuf *h : hb)
                 if (h->p) (void)hipHostFree(h->p);
-            rc_dbuf *db[] = {&sl.d_seq, &sl.d_qual, &sl.d_off, &sl.d_res, &sl.d_packed, &sl.d_exc, &sl.d_fix, &sl.weak.d, &sl.depth.d, &sl.screen.d};
+            rc_dbuf *db[] = {&sl.d_seq, &sl.d_qual, &sl.d_off, &sl.d_res, &sl.d_packed, &sl.d_exc, &sl.d_fix};
             for (rc_dbuf *d : db)
                 if (d->p) (void)hipFree(d->p);
+            for (rc_slot_payload &pl : sl.payload) {
+                if (pl.p.p) (void)hipHostFree(pl.p.p);
+                if (pl.d.p) (void)hipFree(pl.d.p);
+            }
             hipEvent_t ev[] = {sl.e_h2d, sl.e_k, sl.e_done};
             for (hipEvent_t e : ev)
                 if (e) (void)hipEventDestroy(e);

@@ -67,9 +67,8 @@ struct rc_slot {
     rc_slot_out out;
     rc_dbuf d_packed, d_exc, d_fix;
     rc_hbuf p_in, p_fix, p_nfix;
-    // the per-read payloads of the batch in flight, 16 bytes per read each: its weak-k-mer profile (rc_weak_profile_into) and
-    // its k-mer depth (rc_read_depth_into), its hit profile against a second k-mer set (rc_read_screen_into)
-    rc_slot_payload weak, depth, screen;
+    // the per-read payloads of the batch in flight, 16 bytes per read each, by rc_payload_kind
+    rc_slot_payload payload[RC_PAY_COUNT];
     // what the batch observers staged for the batch in flight, until its wait accepts it (a packed / resident batch that did
     // not fit its fix list comes again, and only then counts)
     rc_batch_observed obs;

@@ -18,27 +18,15 @@ static int in_slot_lane(rc_ctx *c, int slot, bool submit, Entry entry)
     if (!c || slot < 0 || slot >= RC_MAX_SLOTS) return RC_ERR_ARG;
     // a submit takes the slot's registrations (rc_weak_profile_into, rc_read_depth_into, rc_read_screen_into) with it, whatever
     // becomes of the submit
-    rc_ctx::rc_weak_reg weak;
-    rc_ctx::rc_depth_reg depth;
-    rc_ctx::rc_screen_reg screen;
-    if (submit) {
-        std::swap(weak, c->weak_reg[slot]);
-        std::swap(depth, c->depth_reg[slot]);
-        std::swap(screen, c->screen_reg[slot]);
-    }
+    rc_ctx::rc_payload_reg reg[RC_PAY_COUNT];
+    if (submit)
+        for (int kind = 0; kind < RC_PAY_COUNT; ++kind) std::swap(reg[kind], c->payload_reg[kind][slot]);
     rc_ctx *ln = rc_slot_lane(c, slot, submit, submit);
     if (!ln) return RC_ERR_HIP;
-    if (submit) {
-        ln->weak_cur = weak;
-        ln->depth_cur = depth;
-        ln->screen_cur = screen;
-    }
+    if (submit) std::copy(reg, reg + RC_PAY_COUNT, ln->payload_cur);
     const int rc = entry(static_cast<rc_ctx_full *>(ln), ln == c ? slot : 0);
-    if (submit) {  // (a submit that returned in front of slot_download: nothing stays behind)
-        ln->weak_cur = rc_ctx::rc_weak_reg();
-        ln->depth_cur = rc_ctx::rc_depth_reg();
-        ln->screen_cur = rc_ctx::rc_screen_reg();
-    }
+    // (a submit that returned in front of slot_download: nothing stays behind)
+    if (submit) std::fill(ln->payload_cur, ln->payload_cur + RC_PAY_COUNT, rc_ctx::rc_payload_reg());
     if (rc && ln != c) rc_lane_error(c, ln);
     return rc;
 }
@@ -53,7 +41,7 @@ static int slot_acquire(rc_ctx_full *ctx, int slot, const char *name, const char
         rc_set_error(ctx, "%s: slot %d still holds a batch (%s first)", name, slot, wait_hint);
         return RC_ERR_STATE;
     }
-    sl.weak.out = sl.depth.out = sl.screen.out = nullptr;  // (slot_download sets them for a batch that has the registration)
+    for (rc_slot_payload &pl : sl.payload) pl.out = nullptr;  // (slot_download sets them for a batch that has the registration)
     sl.obs.reset();         // (rc_correct_observed stages into it what the armed observers take of the batch)
     *out = &sl;
     return RC_OK;
@@ -142,7 +130,7 @@ static int slot_fix_list_target(rc_ctx_full *ctx, const rc_slot &sl, uint32_t **
     return RC_OK;
 }
 
-// A per-read payload (rc_api_internal.h: rc_slot_payload), the three steps of its way.  reserve: the registration's array into
+// A per-read payload (rc_api_internal.h: rc_slot_payload), the steps of its way.  reserve: the registration's array into
 // the slot, with room for the values in HBM and, where the array is not page-locked, in the slot's staging; nothing for out ==
 // nullptr.  download: the 16 bytes per read on the download stream, into the array or the staging.  back: a wait that succeeds
 // hands over what went to the staging.
@@ -153,6 +141,22 @@ static int payload_reserve(rc_ctx_full *ctx, rc_slot_payload &pl, void *out, siz
     if (const int rc = rc_dbuf_reserve(ctx, &pl.d, total * 16)) return rc;
     pl.pinned = rc_is_pinned(out, total * 16);
     return pl.pinned ? (int)RC_OK : rc_hbuf_reserve(ctx, &pl.p, total * 16);
+}
+
+// the kernels of payload `kind` over the slot's corrected arena, on ctx's compute stream, where the batch has the registration
+// -- the one place that knows the kinds apart
+static int payload_launch(rc_ctx_full *ctx, rc_slot &sl, int kind, const rc_ctx::rc_payload_reg &reg)
+{
+    if (!sl.payload[kind].out) return RC_OK;
+    const uint8_t *d_seq = (const uint8_t *)sl.d_seq.p;
+    const uint32_t *d_off = (const uint32_t *)sl.d_off.p;
+    const uint32_t n = (uint32_t)sl.total_reads;
+    void *d_out = sl.payload[kind].d.p;
+    switch (kind) {
+    case RC_PAY_WEAK: return rc_launch_weak_profile(ctx, d_seq, sl.arena_bytes, d_off, n, reg.min_count, &ctx->weak_planes, d_out);
+    case RC_PAY_DEPTH: return rc_launch_read_depth(ctx, d_seq, sl.arena_bytes, d_off, n, d_out);
+    default: return rc_launch_read_screen(ctx, reg.screen, d_seq, sl.arena_bytes, d_off, n, reg.min_count, d_out);
+    }
 }
 
 static int payload_download(rc_ctx_full *ctx, const rc_slot_payload &pl, size_t total)
@@ -168,41 +172,26 @@ static void payload_back(const rc_slot_payload &pl, size_t total)
 
 // Behind the batch's last kernel: what `first` queues on the download stream (the arena, the fix count), then ret / l / m / h to
 // sl.out or the slot's staging.  one_copy: where the caller's four arrays are one block, as the device's are, one copy instead
-// of four.  A batch submitted with a weak-profile registration (rc_weak_profile_into: ctx->weak_cur) has its corrected arena
-// profiled first, behind its last kernel on its own stream, and the 16 bytes per read come down with the results; one with a
-// depth registration (rc_read_depth_into: ctx->depth_cur) has its k-mer depth taken the same way, one with a screen
-// registration (rc_read_screen_into: ctx->screen_cur) its hit profile against the registered context's table.
+// of four.  A batch submitted with a payload registration (rc_api_payload.hip: ctx->payload_cur) has that payload's kernels run
+// over its corrected arena first, behind its last kernel on its own stream, and the 16 bytes per read come down with the
+// results -- weak profile, depth, screen, in rc_payload_kind's order on either stream.
 template <class First>
 static int slot_download(rc_ctx_full *ctx, rc_slot &sl, bool one_copy, First first)
 {
     const size_t total = sl.total_reads;
     const rc_slot_out &o = sl.out;
     const int32_t *d_res = (const int32_t *)sl.d_res.p;
-    const rc_ctx::rc_weak_reg weak = ctx->weak_cur;
-    const rc_ctx::rc_depth_reg depth = ctx->depth_cur;
-    const rc_ctx::rc_screen_reg screen = ctx->screen_cur;
-    ctx->weak_cur = rc_ctx::rc_weak_reg();
-    ctx->depth_cur = rc_ctx::rc_depth_reg();
-    ctx->screen_cur = rc_ctx::rc_screen_reg();
-    sl.depth.out = sl.screen.out = nullptr;
-    int prc;
-    if ((prc = payload_reserve(ctx, sl.weak, weak.out, total))) return prc;
-    if (sl.weak.out && (prc = rc_launch_weak_profile(ctx, (const uint8_t *)sl.d_seq.p, sl.arena_bytes, (const uint32_t *)sl.d_off.p, (uint32_t)total,
-                                                     weak.min_count, &ctx->weak_planes, sl.weak.d.p)))
-        return prc;
-    if ((prc = payload_reserve(ctx, sl.depth, depth.out, total))) return prc;
-    if (sl.depth.out && (prc = rc_launch_read_depth(ctx, (const uint8_t *)sl.d_seq.p, sl.arena_bytes, (const uint32_t *)sl.d_off.p, (uint32_t)total, sl.depth.d.p)))
-        return prc;
-    if ((prc = payload_reserve(ctx, sl.screen, screen.out, total))) return prc;
-    if (sl.screen.out && (prc = rc_launch_read_screen(ctx, screen.screen, (const uint8_t *)sl.d_seq.p, sl.arena_bytes, (const uint32_t *)sl.d_off.p,
-                                                      (uint32_t)total, screen.min_count, sl.screen.d.p)))
-        return prc;
+    rc_ctx::rc_payload_reg reg[RC_PAY_COUNT];
+    for (int kind = 0; kind < RC_PAY_COUNT; ++kind) std::swap(reg[kind], ctx->payload_cur[kind]);
+    for (int kind = 0; kind < RC_PAY_COUNT; ++kind) {
+        if (const int rc = payload_reserve(ctx, sl.payload[kind], reg[kind].out, total)) return rc;
+        if (const int rc = payload_launch(ctx, sl, kind, reg[kind])) return rc;
+    }
     RC_CHECK_HIP(ctx, hipEventRecord(sl.e_k, ctx->stream));
     RC_CHECK_HIP(ctx, hipStreamWaitEvent(ctx->s_d2h, sl.e_k, 0));
     if (const int rc = first()) return rc;
-    if ((prc = payload_download(ctx, sl.weak, total))) return prc;
-    if ((prc = payload_download(ctx, sl.depth, total))) return prc;
-    if ((prc = payload_download(ctx, sl.screen, total))) return prc;
+    for (const rc_slot_payload &pl : sl.payload)
+        if (const int rc = payload_download(ctx, pl, total)) return rc;
     if (!sl.res_pinned) {
         RC_CHECK_HIP(ctx, hipMemcpyAsync(sl.p_res.p, d_res, total * 16, hipMemcpyDeviceToHost, ctx->s_d2h));
     } else if (one_copy && o.l == o.ret + total && o.m == o.l + total && o.h == o.m + total) {
@@ -221,9 +210,7 @@ static int slot_download(rc_ctx_full *ctx, rc_slot &sl, bool one_copy, First fir
 static void slot_results_back(const rc_slot &sl)
 {
     const size_t total = sl.total_reads;
-    payload_back(sl.weak, total);
-    payload_back(sl.depth, total);
-    payload_back(sl.screen, total);
+    for (const rc_slot_payload &pl : sl.payload) payload_back(pl, total);
     if (sl.res_pinned) return;
     const int32_t *r = (const int32_t *)sl.p_res.p;
     memcpy(sl.out.ret, r, total * 4);

@@ -1,23 +1,16 @@
 // rc_depth.hip -- the per-read k-mer depth (include/rcorrector_amd.h: rc_read_depth; arithmetic in rc_depth.h): for every read
 // of an arena the number of its valid k-windows and the lower quartile, median and upper quartile of their counts in the table.
 //
-// One launch.  A workgroup takes RC_DEPTH_BLOCK_READS consecutive reads, a run of them that fits the probe tile at a time: the run
-// is copied into a local arena in LDS and cut into windows exactly as k_probe_list does it (rc_device.h: rc_tile_copy_reads,
-// rc_tile_pack; rc_common.h: rc_tile_window), one bucket probe per valid window -- but the counts stay in LDS, 4 bytes per local
-// position over the bytes the raw copy no longer needs, RC_DEPTH_INVALID for a window that is no k-mer.  A wavefront then takes
-// a read: its lanes hold the read's counts, ceil(windows / 64) each, and rc_depth_select finds the three ranks in one descent
-// over the counts' bits, a ballot and a population count per value slot and question.  16 bytes per read leave the kernel.
-// The arena may start anywhere: reads are copied from the 16-byte boundary at or in front of its first byte, `lead` bytes in
-// front of it (aligned dwords that hold a byte of a read, the bytes outside it masked), and offsets count from lead.
-// No length is trusted: a run ends where the next read would leave the tile, a read beyond the library's limit of
-// RC_MAX_READ_LENGTH - 1 bases or whose offsets leave the arena is no read -- four zeros -- and never staged.
+// One launch.  A workgroup takes RC_RUN_BLOCK_READS consecutive reads, a run of them that fits the probe tile at a time: the run
+// is staged in LDS by rc_tile_stage_run (rc_device.h: where the arena may start, which read is no read -- four zeros here)
+// and cut into windows as k_probe_list does it (rc_common.h: rc_tile_window), one bucket probe per valid window -- but the
+// counts stay in LDS, 4 bytes per local position over the bytes the raw copy no longer needs, RC_DEPTH_INVALID for a window that
+// is no k-mer.  A wavefront then takes a read: its lanes hold the read's counts, ceil(windows / 64) each, and rc_depth_select
+// finds the three ranks in one descent over the counts' bits, a ballot and a population count per value slot and question.
+// 16 bytes per read leave the kernel.
 #include "rc_device.h"
 #include "rc_internal.h"
 #include "rc_depth.h"
-
-#define RC_DEPTH_BLOCK_READS RC_PLIST_MAX_READS
-static_assert(RC_DEPTH_BLOCK_READS <= RC_PROBE_THREADS, "a thread fetches a read's offsets");
-static_assert(4 + 3 + RC_MAX_READ_LENGTH <= RC_PROBE_TILE, "the longest read fits a tile of its own");
 
 // the depth of one read by one wavefront: cnt[0 .. nwin) in LDS, NV * 64 >= nwin
 template <int NV>
@@ -53,43 +46,19 @@ __global__ __launch_bounds__(RC_PROBE_THREADS) void k_read_depth(rc_table_view T
     __shared__ uint32_t s_code[RC_PROBE_TILE / 16 + 4];
     __shared__ uint16_t s_inv[RC_PROBE_TILE / 16 + 4];
     __shared__ uint16_t s_nul[RC_PROBE_TILE / 16 + 4];
-    __shared__ uint32_t s_lpos[RC_DEPTH_BLOCK_READS + 1], s_gpos[RC_DEPTH_BLOCK_READS], s_len1[RC_DEPTH_BLOCK_READS];
+    __shared__ uint32_t s_lpos[RC_RUN_BLOCK_READS + 1], s_gpos[RC_RUN_BLOCK_READS], s_len1[RC_RUN_BLOCK_READS];
     __shared__ uint32_t s_take;
     uint32_t *s_raw = s_cnt;
     const uint32_t t = threadIdx.x, wv = t >> 6, ln = t & 63u;
-    const uint32_t i0 = blockIdx.x * (uint32_t)RC_DEPTH_BLOCK_READS;
-    const uint32_t nr_all = n - i0 < (uint32_t)RC_DEPTH_BLOCK_READS ? n - i0 : (uint32_t)RC_DEPTH_BLOCK_READS;
+    const uint32_t i0 = blockIdx.x * (uint32_t)RC_RUN_BLOCK_READS;
+    const uint32_t nr_all = n - i0 < (uint32_t)RC_RUN_BLOCK_READS ? n - i0 : (uint32_t)RC_RUN_BLOCK_READS;
     const uint32_t *m_inv = reinterpret_cast<const uint32_t *>(s_inv);
     const uint32_t *m_nul = reinterpret_cast<const uint32_t *>(s_nul);
     for (uint32_t done = 0; done < nr_all;) {
-        const uint32_t left = nr_all - done;
-        if (t < left) {
-            const uint32_t r = i0 + done + t, g0 = off[r], g1 = off[r + 1];
-            // (a read is its bases and a NUL; 0 = no read: its offsets leave the arena, or it is longer than any read the library takes)
-            s_len1[t] = g1 > g0 && (size_t)g1 <= nbytes && g1 - g0 <= (uint32_t)RC_MAX_READ_LENGTH ? g1 - g0 : 0u;
-            s_gpos[t] = g0 + lead;
-        }
-        for (uint32_t c = t; c < (RC_PROBE_TILE + 64) / 4; c += RC_PROBE_THREADS) s_raw[c] = 0;
-        __syncthreads();
-        if (t == 0) {  // local start of each read: same alignment modulo 4 as in memory, a NUL in front; the run ends where the tile does
-            uint32_t lp = 4, j = 0;
-            for (; j < left; ++j) {
-                const uint32_t at = ((lp + 3u) & ~3u) + (s_gpos[j] & 3u);
-                if (at + s_len1[j] > (uint32_t)RC_PROBE_TILE) break;  // (never the run's first read: it starts at 4 .. 7)
-                s_lpos[j] = at;
-                lp = at + s_len1[j];
-            }
-            s_lpos[j] = lp;
-            s_take = j;
-        }
-        __syncthreads();
-        const uint32_t nr = s_take, total = s_lpos[nr];
-        rc_tile_copy_reads<RC_PROBE_THREADS>(s_raw, s_gpos, s_lpos, s_len1, nr, seq16, (size_t)lead + nbytes);
-        __syncthreads();
-        for (int chunk = (int)t; chunk < RC_PROBE_TILE / 16 + 2; chunk += RC_PROBE_THREADS)
-            rc_tile_pack(*reinterpret_cast<const uint4 *>(s_raw + 4 * chunk), chunk, s_code, s_inv, s_nul);
-        rc_tile_sentinels(s_code);
-        __syncthreads();  // (from here on s_raw's words are s_cnt's)
+        uint32_t total;  // (the local end of the run's last read)
+        const uint32_t nr = rc_tile_stage_run<RC_PROBE_THREADS>(s_raw, s_code, s_inv, s_nul, s_lpos, s_gpos, s_len1, &s_take, seq16, lead, nbytes, off,
+                                                                i0 + done, nr_all - done, &total);
+        // (from here on s_raw's words are s_cnt's)
 #pragma unroll 2
         for (uint32_t a = 4u + t; a + (uint32_t)k <= total; a += RC_PROBE_THREADS) {
             const rc_tile_win w = rc_tile_window(s_code, m_inv, m_nul, (int)a, k);
@@ -127,7 +96,7 @@ int rc_launch_read_depth(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const
         rc_set_error(ctx, "read_depth: arena of %zu bytes, %u bytes behind a 16-byte boundary, exceeds the 4 GiB batch limit", nbytes, lead);
         return RC_ERR_ARG;
     }
-    const unsigned G = (unsigned)(((uint64_t)n_reads + RC_DEPTH_BLOCK_READS - 1) / RC_DEPTH_BLOCK_READS);
+    const unsigned G = (unsigned)(((uint64_t)n_reads + RC_RUN_BLOCK_READS - 1) / RC_RUN_BLOCK_READS);
     rc_timer_begin(ctx);
     rc_with_ext(ctx->ext, [&](auto ext) {
         hipLaunchKernelGGL(k_read_depth<decltype(ext)::value>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(ctx), d_seq - lead, lead, nbytes, d_off,

@@ -356,6 +356,63 @@ __device__ __forceinline__ void rc_tile_copy_reads(uint32_t *s_raw, const uint32
     }
 }
 
+// ---- a run of consecutive reads in the probe tile (k_read_depth, k_read_screen) --------------------------------------------
+// A workgroup of these kernels takes RC_RUN_BLOCK_READS consecutive reads, a run of them that fits the probe tile at a time.
+#define RC_RUN_BLOCK_READS RC_PLIST_MAX_READS
+static_assert(RC_RUN_BLOCK_READS <= RC_PROBE_THREADS, "a thread fetches a read's offsets");
+static_assert(4 + 3 + RC_MAX_READ_LENGTH <= RC_PROBE_TILE, "the longest read fits a tile of its own");
+
+// rc_tile_stage_run: the next run of a workgroup (NT threads) into its tile -- reads first, first + 1, ... of the `left` the
+// workgroup still has (left >= 1), as many as fit -- copied into the local arena s_raw[(RC_PROBE_TILE + 64) / 4] and packed
+// into the planes rc_tile_window (rc_common.h) cuts a k-mer out of, s_code / s_inv / s_nul[RC_PROBE_TILE / 16 + 4].  Returns
+// the number of reads taken, >= 1, behind the barrier that makes the planes readable; s_raw is free from then on.
+//   The arena may start anywhere: seq16 is the 16-byte boundary at or in front of it, the arena is bytes [lead, lead + nbytes)
+// from there and off counts from its first byte; reads are copied as aligned dwords that hold a byte of a read, the bytes
+// outside it masked (rc_tile_copy_reads).
+//   No length is trusted.  s_len1[j] is read j's bytes with its NUL, and 0 = no read: its offsets do not ascend or leave the
+// arena, or it is longer than RC_MAX_READ_LENGTH - 1 bases, the library's limit.  Such a read is taken with the run but never
+// staged: it has no window, and its caller's result is four zeros.
+//   s_lpos[j] is read j's local start: the same alignment modulo 4 as in memory (s_gpos[j], counted from seq16), a NUL in front
+// of it.  The run ends where the next read would leave the tile -- never at the run's first read, which starts at 4 .. 7 --
+// and s_lpos[taken] is the local end of the run's last read, also handed back in *end where the caller asks for it (read here,
+// in front of the copy: fetched behind the last barrier it cost k_read_depth 0.3 ms of 56.7).  s_take is the word thread 0
+// announces the run's size in.
+template <int NT>
+__device__ __forceinline__ uint32_t rc_tile_stage_run(uint32_t *s_raw, uint32_t *s_code, uint16_t *s_inv, uint16_t *s_nul, uint32_t *s_lpos, uint32_t *s_gpos,
+                                                      uint32_t *s_len1, uint32_t *s_take, const uint8_t *seq16, uint32_t lead, size_t nbytes,
+                                                      const uint32_t *off, uint32_t first, uint32_t left, uint32_t *end = nullptr)
+{
+    const uint32_t t = threadIdx.x;
+    if (t < left) {
+        const uint32_t r = first + t, g0 = off[r], g1 = off[r + 1];
+        s_len1[t] = g1 > g0 && (size_t)g1 <= nbytes && g1 - g0 <= (uint32_t)RC_MAX_READ_LENGTH ? g1 - g0 : 0u;
+        s_gpos[t] = g0 + lead;
+    }
+    for (uint32_t c = t; c < (RC_PROBE_TILE + 64) / 4; c += NT) s_raw[c] = 0;
+    __syncthreads();
+    if (t == 0) {
+        uint32_t lp = 4, j = 0;
+        for (; j < left; ++j) {
+            const uint32_t at = ((lp + 3u) & ~3u) + (s_gpos[j] & 3u);
+            if (at + s_len1[j] > (uint32_t)RC_PROBE_TILE) break;
+            s_lpos[j] = at;
+            lp = at + s_len1[j];
+        }
+        s_lpos[j] = lp;
+        *s_take = j;
+    }
+    __syncthreads();
+    const uint32_t nr = *s_take;
+    if (end) *end = s_lpos[nr];
+    rc_tile_copy_reads<NT>(s_raw, s_gpos, s_lpos, s_len1, nr, seq16, (size_t)lead + nbytes);
+    __syncthreads();
+    for (int chunk = (int)t; chunk < RC_PROBE_TILE / 16 + 2; chunk += NT)
+        rc_tile_pack(*reinterpret_cast<const uint4 *>(s_raw + 4 * chunk), chunk, s_code, s_inv, s_nul);
+    rc_tile_sentinels(s_code);
+    __syncthreads();
+    return nr;
+}
+
 // the live entry stored in slot s of bucket b, if any: its canonical code and count.  A key that was
 // Put more than once occupies several slots; the one a probe reaches first (the latest Put,
 // Store.h:55) is the table's entry, the others are dead.

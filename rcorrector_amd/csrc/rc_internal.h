@@ -68,6 +68,10 @@ struct rc_arena_set {
 
 #define RC_MAX_SLOTS 4
 
+// the per-read payloads a batch of the slot transports can carry, 16 bytes per read each, in the order their kernels are
+// launched and their values come down: the weak-k-mer profile, the k-mer depth, the hit profile against a second k-mer set
+enum rc_payload_kind { RC_PAY_WEAK, RC_PAY_DEPTH, RC_PAY_SCREEN, RC_PAY_COUNT };
+
 // trust profile: the counts of one batch in flight, an rc_trust_counts of its bases as they arrived and one of its bases as
 // corrected, until the batch completes (staged == false: none were taken); gen: the profile they were taken for
 struct rc_trust_staged {
@@ -202,31 +206,20 @@ struct rc_ctx : rc_table_desc {
     unsigned long long *rep_acc = nullptr;
     rc_dbuf rep_snap;
     // weak-k-mer profile (rc_weak_profile_device / rc_weak_profile_into; kernels in rc_weak.hip).  weak_planes: the two bit planes
-    // of the arena profiled last, scratch of the context the kernels run in (they serialise on its compute stream).  weak_reg:
-    // per slot of THIS context's entry points, where the next batch submitted there leaves its reads' profile (out == nullptr:
-    // nowhere) -- the submit takes it and hands it to the context the batch runs in (a lane included) as weak_cur, which the
-    // slot's download step consumes
-    struct rc_weak_reg {
-        void *out = nullptr;  // rc_read_weak[total]
-        int32_t min_count = 1;
-    };
+    // of the arena profiled last, scratch of the context the kernels run in (they serialise on its compute stream)
     rc_dbuf weak_planes;
-    rc_weak_reg weak_reg[4], weak_cur;
-    // k-mer depth (rc_read_depth_device / rc_read_depth_into; kernel in rc_depth.hip): the registrations travel as the weak
-    // profile's do -- depth_reg per slot of this context's entry points, depth_cur in the context the batch runs in
-    struct rc_depth_reg {
-        void *out = nullptr;  // rc_read_depth[total]
+    // The per-read payloads' one-shot registrations (rc_api_payload.hip: rc_weak_profile_into, rc_read_depth_into,
+    // rc_read_screen_into; kernels in rc_weak.hip, rc_depth.hip, rc_screen.hip).  payload_reg[kind][slot]: per slot of THIS
+    // context's entry points, where the next batch submitted there leaves its reads' 16 bytes each (out == nullptr: nowhere) --
+    // the submit takes it and hands it to the context the batch runs in (a lane included) as payload_cur[kind], which the
+    // slot's download step consumes
+    struct rc_payload_reg {
+        void *out = nullptr;             // rc_read_weak / rc_read_depth / rc_read_screen[total]
+        int32_t min_count = 1;           // weak, screen
+        const rc_ctx *screen = nullptr;  // screen: the context whose table the batch's reads are looked up in -- the caller keeps it
+                                         // and its table alive until the batch's wait
     };
-    rc_depth_reg depth_reg[4], depth_cur;
-    // hit profile against a second k-mer set (rc_read_screen_device / rc_read_screen_into; kernel in rc_screen.hip): the
-    // registrations travel the same way; `screen` is the context whose table the batch's reads are looked up in -- the caller
-    // keeps it and its table alive until the batch's wait
-    struct rc_screen_reg {
-        void *out = nullptr;  // rc_read_screen[total]
-        const rc_ctx *screen = nullptr;
-        int32_t min_count = 1;
-    };
-    rc_screen_reg screen_reg[4], screen_cur;
+    rc_payload_reg payload_reg[RC_PAY_COUNT][RC_MAX_SLOTS], payload_cur[RC_PAY_COUNT];
     // duplicate census (rc_dup_census_begin; kernels in rc_dups.hip).  In the context it was opened on (the batches of its slot
     // lanes add to it too: rc_home): the keys of every unit seen, version 0 = before and 1 = after correction, 16 bytes per
     // unit each, dup_n units of dup_cap; dup_gen counts the begins (keys a batch staged for one census never reach the next).

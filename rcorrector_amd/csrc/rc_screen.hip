@@ -2,21 +2,16 @@
 // rc_screen.h): for every read of an arena its valid k-windows, those whose canonical k-mer a SCREEN table -- any context's, not
 // the one the kernel runs in -- holds at least min_count times, the bases such windows cover and their longest run.
 //
-// One launch.  The staging is k_read_depth's (rc_depth.hip): a workgroup takes RC_SCREEN_BLOCK_READS consecutive reads, a run of
-// them that fits the probe tile at a time, copied into a local arena in LDS and packed into the planes rc_tile_window cuts a
-// k-mer out of; the arena may start anywhere (`lead`), no length is trusted, a read whose offsets leave the arena or that is
-// longer than RC_MAX_READ_LENGTH - 1 bases is no read -- four zeros -- and never staged.  What follows differs: nothing but a
-// bit per window has to survive the probe, so no count is kept anywhere.  A wavefront takes a read, 64 windows at a time, one
-// bucket probe per valid window into the screen table, and the two ballots -- valid, hit -- are the next word of the read's
-// masks, uniform in the wavefront: the valid one is counted, the hit one goes through rc_screen_add_word, the same run-by-run
-// walk the host program checks.  16 bytes per read leave the kernel.
+// One launch.  A workgroup takes RC_RUN_BLOCK_READS consecutive reads, a run of them that fits the probe tile at a time, staged
+// in LDS by rc_tile_stage_run (rc_device.h: where the arena may start, which read is no read -- four zeros here), as
+// k_read_depth (rc_depth.hip) does.  What follows differs: nothing but a bit per window has to survive the probe, so no count
+// is kept anywhere.  A wavefront takes a read, 64 windows at a time, one bucket probe per valid window into the screen table,
+// and the two ballots -- valid, hit -- are the next word of the read's masks, uniform in the wavefront: the valid one is
+// counted, the hit one goes through rc_screen_add_word, the same run-by-run walk the host program checks.  16 bytes per read
+// leave the kernel.
 #include "rc_device.h"
 #include "rc_internal.h"
 #include "rc_screen.h"
-
-#define RC_SCREEN_BLOCK_READS RC_PLIST_MAX_READS
-static_assert(RC_SCREEN_BLOCK_READS <= RC_PROBE_THREADS, "a thread fetches a read's offsets");
-static_assert(4 + 3 + RC_MAX_READ_LENGTH <= RC_PROBE_TILE, "the longest read fits a tile of its own");
 
 // S: the screen table.  seq16: the 16-byte boundary at or in front of the arena; the arena is bytes [lead, lead + nbytes) from
 // there, off counts from its first byte.  out[r] is written for every r < n.
@@ -29,42 +24,16 @@ __global__ __launch_bounds__(RC_PROBE_THREADS) void k_read_screen(rc_table_view 
     __shared__ uint32_t s_code[RC_PROBE_TILE / 16 + 4];
     __shared__ uint16_t s_inv[RC_PROBE_TILE / 16 + 4];
     __shared__ uint16_t s_nul[RC_PROBE_TILE / 16 + 4];
-    __shared__ uint32_t s_lpos[RC_SCREEN_BLOCK_READS + 1], s_gpos[RC_SCREEN_BLOCK_READS], s_len1[RC_SCREEN_BLOCK_READS];
+    __shared__ uint32_t s_lpos[RC_RUN_BLOCK_READS + 1], s_gpos[RC_RUN_BLOCK_READS], s_len1[RC_RUN_BLOCK_READS];
     __shared__ uint32_t s_take;
     const uint32_t t = threadIdx.x, wv = t >> 6, ln = t & 63u;
-    const uint32_t i0 = blockIdx.x * (uint32_t)RC_SCREEN_BLOCK_READS;
-    const uint32_t nr_all = n - i0 < (uint32_t)RC_SCREEN_BLOCK_READS ? n - i0 : (uint32_t)RC_SCREEN_BLOCK_READS;
+    const uint32_t i0 = blockIdx.x * (uint32_t)RC_RUN_BLOCK_READS;
+    const uint32_t nr_all = n - i0 < (uint32_t)RC_RUN_BLOCK_READS ? n - i0 : (uint32_t)RC_RUN_BLOCK_READS;
     const uint32_t *m_inv = reinterpret_cast<const uint32_t *>(s_inv);
     const uint32_t *m_nul = reinterpret_cast<const uint32_t *>(s_nul);
     for (uint32_t done = 0; done < nr_all;) {
-        const uint32_t left = nr_all - done;
-        if (t < left) {
-            const uint32_t r = i0 + done + t, g0 = off[r], g1 = off[r + 1];
-            // (a read is its bases and a NUL; 0 = no read: its offsets leave the arena, or it is longer than any read the library takes)
-            s_len1[t] = g1 > g0 && (size_t)g1 <= nbytes && g1 - g0 <= (uint32_t)RC_MAX_READ_LENGTH ? g1 - g0 : 0u;
-            s_gpos[t] = g0 + lead;
-        }
-        for (uint32_t c = t; c < (RC_PROBE_TILE + 64) / 4; c += RC_PROBE_THREADS) s_raw[c] = 0;
-        __syncthreads();
-        if (t == 0) {  // local start of each read: same alignment modulo 4 as in memory, a NUL in front; the run ends where the tile does
-            uint32_t lp = 4, j = 0;
-            for (; j < left; ++j) {
-                const uint32_t at = ((lp + 3u) & ~3u) + (s_gpos[j] & 3u);
-                if (at + s_len1[j] > (uint32_t)RC_PROBE_TILE) break;  // (never the run's first read: it starts at 4 .. 7)
-                s_lpos[j] = at;
-                lp = at + s_len1[j];
-            }
-            s_lpos[j] = lp;
-            s_take = j;
-        }
-        __syncthreads();
-        const uint32_t nr = s_take;
-        rc_tile_copy_reads<RC_PROBE_THREADS>(s_raw, s_gpos, s_lpos, s_len1, nr, seq16, (size_t)lead + nbytes);
-        __syncthreads();
-        for (int chunk = (int)t; chunk < RC_PROBE_TILE / 16 + 2; chunk += RC_PROBE_THREADS)
-            rc_tile_pack(*reinterpret_cast<const uint4 *>(s_raw + 4 * chunk), chunk, s_code, s_inv, s_nul);
-        rc_tile_sentinels(s_code);
-        __syncthreads();
+        const uint32_t nr = rc_tile_stage_run<RC_PROBE_THREADS>(s_raw, s_code, s_inv, s_nul, s_lpos, s_gpos, s_len1, &s_take, seq16, lead, nbytes, off,
+                                                                i0 + done, nr_all - done);
         for (uint32_t j = wv; j < nr; j += RC_PROBE_THREADS / 64) {  // a wavefront per read
             const uint32_t len1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_len1[j]);
             const uint32_t lp = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_lpos[j]);
@@ -107,7 +76,7 @@ int rc_launch_read_screen(rc_ctx *ctx, const rc_ctx *screen, const uint8_t *d_se
         rc_set_error(ctx, "read_screen: arena of %zu bytes, %u bytes behind a 16-byte boundary, exceeds the 4 GiB batch limit", nbytes, lead);
         return RC_ERR_ARG;
     }
-    const unsigned G = (unsigned)(((uint64_t)n_reads + RC_SCREEN_BLOCK_READS - 1) / RC_SCREEN_BLOCK_READS);
+    const unsigned G = (unsigned)(((uint64_t)n_reads + RC_RUN_BLOCK_READS - 1) / RC_RUN_BLOCK_READS);
     rc_timer_begin(ctx);
     rc_with_ext(screen->ext, [&](auto ext) {  // (the screen table's layout, not the context's)
         hipLaunchKernelGGL(k_read_screen<decltype(ext)::value>, dim3(G), dim3(RC_PROBE_THREADS), 0, ctx->stream, rc_view(screen), d_seq - lead, lead, nbytes,
