@@ -627,6 +627,57 @@ int rc_mate_overlap_begin(rc_ctx *ctx, int32_t min_overlap, int32_t max_mismatch
 int rc_mate_overlap_get(rc_ctx *ctx, rc_mate_overlap *out);
 int rc_mate_overlap_end(rc_ctx *ctx);
 
+/* ---- read trimming: how many bases of every read to keep -------------------------------------------------------------------
+ * The step between a corrector and an assembler that recipes hand to a separate CPU program: a 3' quality cut, a 3' adapter
+ * cut, and for pairs the cut of a mate that ran through a short fragment into the adapter.  For a read of L bases (at most 1023)
+ * three independent cuts are taken on the read AS GIVEN, each a position in 0 .. L, L meaning "no cut" (rc_trim.h, integer
+ * arithmetic throughout):
+ *   cut_qual     BWA's and cutadapt's 3' rule at q = qual_min: S(i) = the sum over j >= i of q - (Q[j] - qual_base), S(L) = 0; i0 =
+ *                the largest i with S(i) < 0 (-1: none); the cut is the largest i in (i0, L] at which S is maximal.  The stop at i0
+ *                is part of the rule: a bad head behind a good middle is not trimmed.  qual_min = 0 or d_qual = NULL: L
+ *   cut_adapter  adapter1 for mate 1, adapter2 for mate 2 (single reads are mate 1), 0 .. 64 bases of upper-case ACGT, length 0
+ *                switches the cut off.  At offset d in 0 .. L - 1 read position i faces adapter base i - d; v(d) = the faced
+ *                positions whose read base is upper-case ACGT, m(d) = those of them that differ; d is accepted if
+ *                v >= adapter_min and 100 m <= adapter_mm_pct v; the cut is the smallest accepted d, else L.  Hamming only
+ *   cut_pair     modes 1 and 2 with pair_overlap != 0: d* chosen exactly as the mate-overlap report chooses it (above) with
+ *                pair_min_overlap and pair_mm_pct, over the bases as given; F = d* + Lb is the fragment's length, mate 1 keeps
+ *                min(La, F) bases and mate 2 min(Lb, Lb + d*).  No accepted offset: L
+ *   keep_len     min(cut_qual, cut_adapter, cut_pair)
+ * A UNIT (a read in mode 0; read u with read n_reads / 2 + u in mode 1; reads 2u and 2u + 1 in mode 2: the duplicate census's
+ * modes) is KEPT if every mate has keep_len >= min_len, else it is SHORT: a short mate drops its partner too.  Nothing is cut
+ * or dropped here: the call says where to cut.  Not in scope: a compacted, trimmed arena written on the device, 5' trimming,
+ * indels in the adapter alignment, a slot-transport registration.  No byte parity with cutadapt, TrimGalore or fastp is claimed.
+ * No reference counterpart. */
+typedef struct { int32_t keep_len, cut_qual, cut_adapter, cut_pair; } rc_read_trim;        /* 16 bytes per read */
+typedef struct {
+    int32_t qual_min, qual_base, adapter_min, adapter_mm_pct, pair_overlap, pair_min_overlap, pair_mm_pct, min_len;
+    uint8_t adapter1[64], adapter2[64];
+    int32_t adapter1_len, adapter2_len;
+} rc_trim_params;
+typedef struct {
+    uint64_t reads[2];           /* by mate */
+    uint64_t cut_reads[2][3];    /* [mate][quality, adapter, pair]: the reads whose cut is below L */
+    uint64_t bases_removed[2];   /* the sum of L - keep_len */
+    uint64_t short_reads[2];     /* the reads with keep_len < min_len */
+    uint64_t units, units_kept;
+    uint64_t pairs_overlapping;  /* the pairs with an accepted offset */
+    uint64_t keep_hist[2][1024]; /* [mate][keep_len], every read, of kept and of short units alike */
+} rc_trim_tally;
+/* The reads of an arena in HBM: read r the NUL-terminated string at d_off[r] of d_seq, and of d_qual (may be NULL) its quality
+ * bytes; d_off has n_reads + 1 entries.  d_out[r] = the rc_read_trim of read r; d_keep (may be NULL): one byte per unit, 1 kept,
+ * 0 short; d_tally (may be NULL): an rc_trim_tally in HBM that the call ADDS to -- the caller zeroes it.  Asynchronous on the
+ * context's stream (rc_sync() to wait); needs no table.  Neither arena is written; both may be read in aligned 16-byte pieces up
+ * to 15 bytes in front of their first and behind their last byte.  max_read_len, the longest read in bases, picks the kernel
+ * instance (up to 256 bases, or up to 1023); a mate longer than its instance holds is cut to that first, so a wrong max_read_len
+ * can never index outside the arrays.  n_reads == 0: RC_STATUS_OK, no launch.  RC_STATUS_ARG (checked whatever n_reads is): a
+ * mode outside 0 .. 2, an odd n_reads in modes 1 and 2, params == NULL, nbytes >= 2^32, max_read_len outside 0 .. 1023, qual_min
+ * outside 0 .. 93, qual_base outside 0 .. 255, adapter_min outside 1 .. 64, adapter_mm_pct or pair_mm_pct outside 0 .. 50,
+ * pair_min_overlap outside 1 .. 1023, min_len outside 0 .. 1023, an adapter length outside 0 .. 64 or an adapter base outside
+ * ACGT; with n_reads > 0: d_seq, d_off or d_out NULL, d_out off a 4-byte or d_tally off an 8-byte boundary. */
+int rc_read_trim_device(rc_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual, const uint32_t *d_off, uint32_t n_reads, uint64_t nbytes,
+                        int32_t max_read_len, int32_t mode, const rc_trim_params *params, rc_read_trim *d_out, uint8_t *d_keep,
+                        rc_trim_tally *d_tally);
+
 /* ---- run parameters (globals of main.cpp:17-30) ----------------------------------------------- */
 /* replaces main.cpp:310-358 (ERROR_RATE estimation).  Uses the entries parsed by the last
  * rc_table_load_jfdump() in file order -- or, for a table that was counted here or built from

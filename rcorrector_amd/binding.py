@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "rc_recur_census_begin", "rc_recur_census_get", "rc_recur_census_end", "rc_recur_census_merge", "rc_change_keys_device",
     "rc_trust_profile_device", "rc_trust_profile_begin", "rc_trust_profile_get", "rc_trust_profile_end",
     "rc_mate_overlap_device", "rc_mate_overlap_begin", "rc_mate_overlap_get", "rc_mate_overlap_end",
+    "rc_read_trim_device",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
@@ -183,6 +184,50 @@ def mate_overlap_dict(words):
     return out
 
 
+TRIM_MAX_LEN = 1023
+TRIM_ADAPTER_MAX = 64
+TRIM_ADAPTER = b"AGATCGGAAGAGC"      # the Illumina universal stem
+READ_TRIM_DTYPE = np.dtype([("keep_len", np.int32), ("cut_qual", np.int32), ("cut_adapter", np.int32), ("cut_pair", np.int32)])     # rc_read_trim
+TRIM_TALLY_DTYPE = np.dtype([("reads", np.uint64, (2,)), ("cut_reads", np.uint64, (2, 3)), ("bases_removed", np.uint64, (2,)),
+                             ("short_reads", np.uint64, (2,)), ("units", np.uint64), ("units_kept", np.uint64), ("pairs_overlapping", np.uint64),
+                             ("keep_hist", np.uint64, (2, 1024))])                                                                  # rc_trim_tally
+TRIM_TALLY_WORDS = TRIM_TALLY_DTYPE.itemsize // 8
+
+
+class _TrimParams(C.Structure):
+    """rc_trim_params"""
+    _fields_ = [("qual_min", C.c_int32), ("qual_base", C.c_int32), ("adapter_min", C.c_int32), ("adapter_mm_pct", C.c_int32), ("pair_overlap", C.c_int32),
+                ("pair_min_overlap", C.c_int32), ("pair_mm_pct", C.c_int32), ("min_len", C.c_int32), ("adapter1", C.c_uint8 * 64), ("adapter2", C.c_uint8 * 64),
+                ("adapter1_len", C.c_int32), ("adapter2_len", C.c_int32)]
+
+
+def trim_params(qual_min=20, qual_base=33, adapter1=TRIM_ADAPTER, adapter2=None, adapter_min=5, adapter_mm_pct=10, pair_overlap=True, pair_min_overlap=30,
+                pair_mm_pct=10, min_len=20, adapter1_len=None, adapter2_len=None):
+    """an rc_trim_params; adapter2 = None: adapter1's.  Nothing is checked here but what the struct cannot hold (an adapter of
+    more than 64 bytes); adapter*_len overrides the length the library is told."""
+    a1 = bytes(adapter1)
+    a2 = a1 if adapter2 is None else bytes(adapter2)
+    if len(a1) > TRIM_ADAPTER_MAX or len(a2) > TRIM_ADAPTER_MAX:
+        raise ValueError("an adapter has at most %d bases" % TRIM_ADAPTER_MAX)
+    p = _TrimParams(int(qual_min), int(qual_base), int(adapter_min), int(adapter_mm_pct), int(bool(pair_overlap)), int(pair_min_overlap), int(pair_mm_pct),
+                    int(min_len))
+    C.memmove(p.adapter1, a1, len(a1))
+    C.memmove(p.adapter2, a2, len(a2))
+    p.adapter1_len = len(a1) if adapter1_len is None else int(adapter1_len)
+    p.adapter2_len = len(a2) if adapter2_len is None else int(adapter2_len)
+    return p
+
+
+def trim_tally_dict(words):
+    """TRIM_TALLY_WORDS 64-bit words laid out as an rc_trim_tally (a copy of device memory, say) -> a dict named as the struct's
+    fields: ints and numpy uint64 arrays"""
+    w = np.ascontiguousarray(words).view(np.uint64).reshape(-1)
+    if w.size != TRIM_TALLY_WORDS:
+        raise ValueError("an rc_trim_tally has %d 64-bit words, got %d" % (TRIM_TALLY_WORDS, w.size))
+    t = w.view(TRIM_TALLY_DTYPE)[0]
+    return {n: (int(t[n]) if t[n].shape == () else t[n].copy()) for n in TRIM_TALLY_DTYPE.names}
+
+
 class _DeviceBatch(C.Structure):
     _fields_ = [("mode", C.c_int), ("n_reads", C.c_uint32), ("nbytes", C.c_uint64),
                 ("max_read_len", C.c_int32),
@@ -283,6 +328,7 @@ def load_library():
     L.rc_trust_profile_end.argtypes = [vp]
     L.rc_mate_overlap_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
     L.rc_mate_overlap_begin.argtypes = [vp, C.c_int32, C.c_int32]
+    L.rc_read_trim_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(_TrimParams), vp, vp, vp]
     L.rc_mate_overlap_get.argtypes = [vp, C.POINTER(_MateOverlap)]
     L.rc_mate_overlap_end.argtypes = [vp]
     L.rc_estimate_error_rate.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
@@ -622,6 +668,17 @@ class Context:
         units of the whole input in front of this batch.  Needs no table.  Asynchronous: sync() to wait."""
         self._ck(self._L.rc_norm_select_device(self._h, _ptr(d_depth), int(n_units), int(mode), int(unit_base), int(target), int(min_cov), int(seed),
                                                int(max_bin), _ptr(d_keep), _ptr(d_tally)))
+
+    # ---- read trimming: per read, how many bases to keep after the quality, adapter and pair cuts ----
+    def read_trim_device(self, d_seq, d_qual, d_off, n_reads, nbytes, max_read_len, mode, params, d_out, d_keep=None, d_tally=None):
+        """rc_read_trim_device: the reads of an arena in HBM as they are, d_qual (may be None) their quality bytes at the same
+        offsets; params: trim_params(...) (None: the defaults); d_out: device memory for n_reads x 4 int32 (keep_len, cut_qual,
+        cut_adapter, cut_pair: READ_TRIM_DTYPE); d_keep (may be None): one byte per unit, 1 kept, 0 short; the counts are ADDED to
+        d_tally (may be None): device memory for TRIM_TALLY_WORDS uint64, zeroed by the caller (trim_tally_dict reads a copy of
+        it).  Needs no table.  Asynchronous: sync() to wait."""
+        p = trim_params() if params is None else params
+        self._ck(self._L.rc_read_trim_device(self._h, _ptr(d_seq), _ptr(d_qual), _ptr(d_off), int(n_reads), int(nbytes), int(max_read_len), int(mode),
+                                             C.byref(p), _ptr(d_out), _ptr(d_keep), _ptr(d_tally)))
 
     # ---- per-read screen against a second k-mer set: valid and hit windows, covered bases, longest run of hits ----
     def read_screen_device(self, screen, d_seq, d_off, n_reads, nbytes, max_read_len, d_out, min_count=1):

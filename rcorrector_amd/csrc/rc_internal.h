@@ -446,6 +446,11 @@ int rc_launch_trust_add(rc_ctx *ctx, const void *d_src, void *d_dst, uint32_t n_
 int rc_launch_mate_overlap(rc_ctx *ctx, const uint8_t *d_before, const uint8_t *d_after, size_t nbytes, const uint32_t *d_off, uint32_t n_reads,
                            int max_read_len, int mode, int min_overlap, int max_mismatch_pct, void *d_counts);
 
+// rc_trim.hip: d_out[r] = the rc_read_trim of read r (rc_trim.h), d_keep[u] (may be null) = unit u is kept, the counts added to
+// d_tally (an rc_trim_tally in HBM, may be null); one launch, no table; max_read_len picks the instance.  params: an rc_trim_params that has been checked
+int rc_launch_read_trim(rc_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int max_read_len,
+                        int mode, const void *params, void *d_out, uint8_t *d_keep, void *d_tally);
+
 // rc_dups.hip: one 128-bit key per unit of an arena (mode as rc_device_batch: n_reads units, or n_reads / 2 pairs) on stream st;
 // the census of n keys in HBM (left as they are) into host arrays copies[max_bin + 1], *distinct -- synchronous
 int rc_launch_read_keys(rc_ctx *ctx, hipStream_t st, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int mode,

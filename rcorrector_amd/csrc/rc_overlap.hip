@@ -23,6 +23,7 @@
 #include "../../include/rcorrector_amd.h"
 #include "rc_internal.h"
 #include "rc_overlap.h"
+#include "rc_overlap_stage.h"  // rc_ov_wave_sync, rc_ov_chunk
 
 #define RC_OV_THREADS 256
 #define RC_OV_WAVES (RC_OV_THREADS / 64)
@@ -50,38 +51,6 @@ struct rc_overlap_args {
     int min_overlap, max_mismatch_pct;
     unsigned long long *out;  // an rc_mate_overlap
 };
-
-__device__ __forceinline__ void rc_ov_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// chunk c of the read of len bases at arena byte o: half a word of its strings (0 / not valid behind the read's end)
-__device__ __forceinline__ void rc_ov_chunk(const uint8_t *__restrict__ seq, uint32_t o, uint32_t len, uint32_t c, uint32_t &code, uint32_t &val)
-{
-    uint32_t w[4] = {0, 0, 0, 0};
-    if (16u * c < len) {
-        const uintptr_t s = (uintptr_t)(seq + o), a0 = s & ~(uintptr_t)15;
-        const uint32_t lead = (uint32_t)(s - a0), n_pc = (lead + len + 15u) >> 4;  // aligned pieces that hold a byte of the read
-        const uint4 *pc = reinterpret_cast<const uint4 *>(a0) + c;
-        const uint4 p0 = pc[0];  // (16 c < len: holds a byte of the read)
-        uint4 p1 = make_uint4(0, 0, 0, 0);
-        if (lead && c + 1u < n_pc) p1 = pc[1];  // (holds one too)
-        typedef unsigned __int128 u128;
-        const u128 lo = ((u128)(((uint64_t)p0.w << 32) | p0.z) << 64) | (((uint64_t)p0.y << 32) | p0.x);
-        const u128 hi = ((u128)(((uint64_t)p1.w << 32) | p1.z) << 64) | (((uint64_t)p1.y << 32) | p1.x);
-        u128 ch = lead ? (lo >> (8u * lead)) | (hi << (128u - 8u * lead)) : lo;
-        const uint32_t left = len - 16u * c;  // bytes of the chunk inside the read
-        if (left < 16u) ch &= (((u128)1) << (8u * left)) - 1;
-        w[0] = (uint32_t)ch;
-        w[1] = (uint32_t)(ch >> 32);
-        w[2] = (uint32_t)(ch >> 64);
-        w[3] = (uint32_t)(ch >> 96);
-    }
-    rc_ov_pack16(w, code, val);
-}
 
 // NW: 64-bit words a mate's strings have
 template <int NW>
