@@ -92,8 +92,8 @@ int rc_launch_read_depth(rc_ctx *ctx, const uint8_t *d_seq, size_t nbytes, const
     }
     static_assert(sizeof(rc_depth_vals) == 16, "rc_read_depth");
     const uint32_t lead = (uint32_t)((uintptr_t)d_seq & 15u);
-    if ((uint64_t)lead + nbytes >= (1ull << 32)) {  // (the kernel's 32-bit positions count from the boundary in front of the arena)
-        rc_set_error(ctx, "read_depth: arena of %zu bytes, %u bytes behind a 16-byte boundary, exceeds the 4 GiB batch limit", nbytes, lead);
+    if ((uint64_t)nbytes >= (1ull << 32)) {  // (wherever it starts: rc_tile_stage_run's positions from the boundary in front of it may pass 2^32)
+        rc_set_error(ctx, "read_depth: arena of %zu bytes exceeds the 4 GiB batch limit", nbytes);
         return RC_ERR_ARG;
     }
     const unsigned G = (unsigned)(((uint64_t)n_reads + RC_RUN_BLOCK_READS - 1) / RC_RUN_BLOCK_READS);

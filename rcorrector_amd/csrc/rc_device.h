@@ -338,7 +338,7 @@ __device__ __forceinline__ void rc_tile_copy_reads(uint32_t *s_raw, const uint32
     for (uint32_t j = t >> 6; j < nr; j += NT / 64) {
         if (!s_len1[j]) continue;
         const uint32_t g0 = s_gpos[j], lp = s_lpos[j], g1 = g0 + s_len1[j] - 1;  // [g0, g1): the bases
-        const uint32_t w0 = g0 >> 2, w1 = (g1 + 3) >> 2;
+        const uint32_t w0 = g0 >> 2, w1 = (g1 >> 2) + ((g1 & 3u) != 0);  // (g1 + 3 may pass 2^32: the arena's last read)
         for (uint32_t w = w0 + (t & 63u); w < w1; w += 64u) {
             uint32_t v;
             if ((size_t)4 * w + 4 <= nbytes) {
@@ -348,10 +348,45 @@ __device__ __forceinline__ void rc_tile_copy_reads(uint32_t *s_raw, const uint32
                 for (size_t q = 0; (size_t)4 * w + q < nbytes; ++q) v |= (uint32_t)seq[(size_t)4 * w + q] << (8 * q);
             }
             const uint32_t lo = 4 * w < g0 ? g0 - 4 * w : 0, hi = 4 * w + 4 > g1 ? 4 * w + 4 - g1 : 0;  // bytes to drop at either end
+            // (4 * w + 4 is 0 for the dword that ends at 2^32, and hi with it: what it would drop there is the read's NUL and, behind it,
+            // byte 2^32 - 2 -- the NUL of an empty read, a byte outside the arena, which is not loaded, or, where d_off[n] < nbytes, a
+            // byte of the arena that belongs to no read: kept in the tile, but between the read's NUL and the next NUL, where no
+            // window reaches it)
             uint32_t m = 0xFFFFFFFFu;
             if (lo) m &= 0xFFFFFFFFu << (8 * lo);
             if (hi) m &= 0xFFFFFFFFu >> (8 * hi);
             s_raw[(lp >> 2) + (w - w0)] = v & m;
+        }
+    }
+}
+
+// rc_tile_copy_reads_run: the same copy for rc_tile_stage_run, whose positions count from the 16-byte boundary `lead` bytes in
+// front of an arena of up to 2^32 - 1 bytes and so may pass 2^32: s_gpos[j] is the read's start modulo 2^32 -- a start below
+// `lead` is one that wrapped -- and the copy counts dwords and bytes from the read's first dword, never arena positions, in 32
+// bits; only the address is wider.  (rc_tile_copy_reads takes positions below 2^32 and never adds to one.)
+template <int NT>
+__device__ __forceinline__ void rc_tile_copy_reads_run(uint32_t *s_raw, const uint32_t *s_gpos, const uint32_t *s_lpos, const uint32_t *s_len1, uint32_t nr,
+                                                   const uint8_t *__restrict__ seq, size_t nbytes, uint32_t lead)
+{
+    const uint32_t t = threadIdx.x;
+    for (uint32_t j = t >> 6; j < nr; j += NT / 64) {
+        if (!s_len1[j]) continue;
+        const uint32_t g0 = s_gpos[j], lp = s_lpos[j], b0 = g0 & 3u, e = b0 + s_len1[j] - 1;  // the bases: bytes [b0, e) of the dwords from w0 on
+        const uint32_t w0 = (g0 >> 2) + (g0 < lead ? 1u << 30 : 0u), nw = (e + 3) >> 2;    // (at most 2^30 + 3)
+        for (uint32_t i = t & 63u; i < nw; i += 64u) {
+            const size_t at = (size_t)4 * (w0 + i);
+            uint32_t v;
+            if (at + 4 <= nbytes) {
+                v = *reinterpret_cast<const uint32_t *>(seq + at);
+            } else {
+                v = 0;
+                for (size_t q = 0; at + q < nbytes; ++q) v |= (uint32_t)seq[at + q] << (8 * q);
+            }
+            const uint32_t lo = i ? 0u : b0, hi = 4 * i + 4 > e ? 4 * i + 4 - e : 0;  // bytes to drop at either end
+            uint32_t m = 0xFFFFFFFFu;
+            if (lo) m &= 0xFFFFFFFFu << (8 * lo);
+            if (hi) m &= 0xFFFFFFFFu >> (8 * hi);
+            s_raw[(lp >> 2) + i] = v & m;
         }
     }
 }
@@ -368,7 +403,8 @@ static_assert(4 + 3 + RC_MAX_READ_LENGTH <= RC_PROBE_TILE, "the longest read fit
 // the number of reads taken, >= 1, behind the barrier that makes the planes readable; s_raw is free from then on.
 //   The arena may start anywhere: seq16 is the 16-byte boundary at or in front of it, the arena is bytes [lead, lead + nbytes)
 // from there and off counts from its first byte; reads are copied as aligned dwords that hold a byte of a read, the bytes
-// outside it masked (rc_tile_copy_reads).
+// outside it masked (rc_tile_copy_reads_run: rc_tile_copy_reads' loop with the dword index formed another way -- keep the two
+// in step).
 //   No length is trusted.  s_len1[j] is read j's bytes with its NUL, and 0 = no read: its offsets do not ascend or leave the
 // arena, or it is longer than RC_MAX_READ_LENGTH - 1 bases, the library's limit.  Such a read is taken with the run but never
 // staged: it has no window, and its caller's result is four zeros.
@@ -386,7 +422,7 @@ __device__ __forceinline__ uint32_t rc_tile_stage_run(uint32_t *s_raw, uint32_t 
     if (t < left) {
         const uint32_t r = first + t, g0 = off[r], g1 = off[r + 1];
         s_len1[t] = g1 > g0 && (size_t)g1 <= nbytes && g1 - g0 <= (uint32_t)RC_MAX_READ_LENGTH ? g1 - g0 : 0u;
-        s_gpos[t] = g0 + lead;
+        s_gpos[t] = g0 + lead;  // modulo 2^32: only its low bits and, in rc_tile_copy_reads_run, "below lead = wrapped" are used
     }
     for (uint32_t c = t; c < (RC_PROBE_TILE + 64) / 4; c += NT) s_raw[c] = 0;
     __syncthreads();
@@ -404,7 +440,7 @@ __device__ __forceinline__ uint32_t rc_tile_stage_run(uint32_t *s_raw, uint32_t 
     __syncthreads();
     const uint32_t nr = *s_take;
     if (end) *end = s_lpos[nr];
-    rc_tile_copy_reads<NT>(s_raw, s_gpos, s_lpos, s_len1, nr, seq16, (size_t)lead + nbytes);
+    rc_tile_copy_reads_run<NT>(s_raw, s_gpos, s_lpos, s_len1, nr, seq16, (size_t)lead + nbytes, lead);
     __syncthreads();
     for (int chunk = (int)t; chunk < RC_PROBE_TILE / 16 + 2; chunk += NT)
         rc_tile_pack(*reinterpret_cast<const uint4 *>(s_raw + 4 * chunk), chunk, s_code, s_inv, s_nul);
