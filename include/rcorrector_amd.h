@@ -678,6 +678,60 @@ int rc_read_trim_device(rc_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual
                         int32_t max_read_len, int32_t mode, const rc_trim_params *params, rc_read_trim *d_out, uint8_t *d_keep,
                         rc_trim_tally *d_tally);
 
+/* ---- read merging: one fragment-long read from two overlapping mates, written on the device ---------------------------------
+ * What an overlap is most often used for, and what recipes hand to FLASH, PEAR, BBMerge or fastp --merge.  A pair is a (mate 1,
+ * La bases) and b (mate 2, Lb bases); r is the reverse complement of b and at offset d, a[i] faces r[i - d] (the mate-overlap
+ * report, above).  d* is chosen exactly as that report and rc_read_trim_device's pair cut choose it, with min_overlap and
+ * max_mismatch_pct over the bases as given; with no accepted offset the pair is UNMERGED: merged_len = 0 and d = v = m = 0 in its
+ * row.  The merged read has F = d* + Lb bases (the pair cut's fragment length); position p is covered by a when p < La and by r,
+ * at r[p - d*], when p >= d*; what lies outside -- r[0 .. -d* - 1] for d* < 0, a[F ..] for F < La -- is read-through and is
+ * dropped.  Per position (rc_merge.h, integer arithmetic), a base valid when it is upper-case ACGT, p(Q) = max(0, Q - qual_base):
+ *   covered by one mate       that mate's base byte (mate 2's complemented: ACGT <-> TGCA, acgt <-> tgca, every other byte as it
+ *                             is) and its quality byte, verbatim
+ *   both valid and equal      that base, quality qual_base + min(pa + pb, qual_cap)
+ *   both valid and different  the mate with the larger phred value wins, a tie goes to mate 1; quality
+ *                             qual_base + min(max(|pa - pb|, 2), qual_cap)
+ *   exactly one valid         that mate's base byte and quality byte, verbatim
+ *   neither valid             mate 1's two bytes, verbatim
+ *   d_qual == NULL (FASTA)    a disagreement keeps mate 1's base and counts as a tie; no quality arena is written
+ * A mate has at most 1023 bases; a merged read may have up to La + Lb - min_overlap <= 2045.  Of a read longer than 1023 bases
+ * rc_read_trim_device and rc_mate_overlap_device look only at the first 1023; the entry points that stage reads in the probe tile
+ * (rc_read_depth_device, rc_read_screen_device, rc_weak_profile_device) take it as no read: four zeros.  Not in scope: merging inside rcorrector, a slot-transport registration,
+ * a compacted trimmed arena, indel-tolerant overlap, posterior-probability quality models.  No byte parity with FLASH, PEAR or
+ * fastp is claimed.  No reference counterpart. */
+#define RC_MERGE_LEN_BINS 2048
+typedef struct { int32_t merged_len, d, v, m; } rc_read_merge;     /* 16 bytes per unit: v faced valid positions at d, m of them differ */
+typedef struct { int32_t min_overlap, max_mismatch_pct, qual_base, qual_cap; } rc_merge_params;   /* defaults 30, 10, 33, 41 */
+typedef struct {
+    uint64_t pairs, merged, unmerged;
+    uint64_t readthrough;            /* merged with d* < 0 or F < La */
+    uint64_t compared, mismatches;   /* the sums of v and of m over the merged pairs */
+    uint64_t took_mate1, took_mate2, ties;   /* the disagreements by the mate whose base was kept: their sum is `mismatches` */
+    uint64_t len_hist[RC_MERGE_LEN_BINS];    /* [merged_len], every pair: bin 0 holds the unmerged ones */
+} rc_merge_tally;
+/* The pairs of an arena in HBM (read r the NUL-terminated string at d_off[r] of d_seq, and of d_qual -- may be NULL -- its
+ * quality bytes; d_off has n_reads + 1 entries) in mode 1 (read u with read n_reads / 2 + u) or 2 (reads 2u and 2u + 1), units =
+ * n_reads / 2 of them.  d_rows[u] = the rc_read_merge of unit u.  The result is a NEW, compact arena: d_moff has units + 1
+ * entries, unit u's merged read is the NUL-terminated string at d_moff[u] of d_mseq, an unmerged unit an empty string, and
+ * d_moff[units] is the arena's size; d_mqual (may be NULL; must be NULL if d_qual is) gets the quality bytes at the same
+ * offsets.  d_mseq / d_mqual / d_moff with units reads is an arena every per-read entry point accepts as it is in mode 0.
+ * Output size: a merged unit takes F + 1 <= La + Lb + 2 - min_overlap bytes, an unmerged one 1 byte, and the two mates took
+ * La + Lb + 2 bytes of the input: out_cap, the bytes d_mseq (and d_mqual) can hold, must be >= nbytes, and that is always
+ * enough.  No byte at or behind d_moff[units] is written, and nothing is read from the output arenas.  d_tally (may be NULL): an
+ * rc_merge_tally in HBM that the call ADDS to -- the caller zeroes it.  Three steps on the context's stream, asynchronous
+ * (rc_sync() to wait): a plan kernel (the offset scan: rows and lengths), an exclusive scan of the lengths, a write kernel.
+ * Needs no table; neither input arena is written, both may be read in aligned 16-byte pieces up to 15 bytes in front of their
+ * first and behind their last byte.  max_read_len picks the kernel instance (up to 256 bases, or up to 1023); a mate longer than
+ * its instance holds is cut to that first.  n_reads == 0: RC_STATUS_OK, no launch, nothing written.  RC_STATUS_ARG (checked
+ * whatever n_reads is): a mode outside 1 .. 2, an odd n_reads, params == NULL, nbytes >= 2^32, max_read_len outside 0 .. 1023,
+ * min_overlap outside 1 .. 1023, max_mismatch_pct outside 0 .. 50, qual_base outside 0 .. 124, qual_cap outside 2 .. 93,
+ * qual_base + qual_cap > 126, d_mqual given without d_qual, out_cap < nbytes; with n_reads > 0: d_seq, d_off, d_rows, d_mseq or
+ * d_moff NULL, d_rows or d_moff off a 4-byte boundary, d_mseq or d_mqual off a 16-byte one, d_tally
+ * off an 8-byte one. */
+int rc_read_merge_device(rc_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual, const uint32_t *d_off, uint32_t n_reads, uint64_t nbytes,
+                         int32_t max_read_len, int32_t mode, const rc_merge_params *params, rc_read_merge *d_rows,
+                         uint8_t *d_mseq, uint8_t *d_mqual, uint32_t *d_moff, uint64_t out_cap, rc_merge_tally *d_tally);
+
 /* ---- run parameters (globals of main.cpp:17-30) ----------------------------------------------- */
 /* replaces main.cpp:310-358 (ERROR_RATE estimation).  Uses the entries parsed by the last
  * rc_table_load_jfdump() in file order -- or, for a table that was counted here or built from

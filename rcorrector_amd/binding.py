@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "rc_trust_profile_device", "rc_trust_profile_begin", "rc_trust_profile_get", "rc_trust_profile_end",
     "rc_mate_overlap_device", "rc_mate_overlap_begin", "rc_mate_overlap_get", "rc_mate_overlap_end",
     "rc_read_trim_device",
+    "rc_read_merge_device",
     "rc_estimate_error_rate", "rc_bad_quality_from_hist", "rc_set_run_params", "rc_set_quality_bits", "rc_pack_quality_bits",
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
@@ -228,6 +229,35 @@ def trim_tally_dict(words):
     return {n: (int(t[n]) if t[n].shape == () else t[n].copy()) for n in TRIM_TALLY_DTYPE.names}
 
 
+MERGE_MAX_LEN = 1023          # bases of a mate; a merged read has up to 2 * 1023 - min_overlap
+MERGE_LEN_BINS = 2048
+READ_MERGE_DTYPE = np.dtype([("merged_len", np.int32), ("d", np.int32), ("v", np.int32), ("m", np.int32)])     # rc_read_merge
+MERGE_TALLY_DTYPE = np.dtype([("pairs", np.uint64), ("merged", np.uint64), ("unmerged", np.uint64), ("readthrough", np.uint64), ("compared", np.uint64),
+                              ("mismatches", np.uint64), ("took_mate1", np.uint64), ("took_mate2", np.uint64), ("ties", np.uint64),
+                              ("len_hist", np.uint64, (MERGE_LEN_BINS,))])                                      # rc_merge_tally
+MERGE_TALLY_WORDS = MERGE_TALLY_DTYPE.itemsize // 8
+
+
+class _MergeParams(C.Structure):
+    """rc_merge_params"""
+    _fields_ = [("min_overlap", C.c_int32), ("max_mismatch_pct", C.c_int32), ("qual_base", C.c_int32), ("qual_cap", C.c_int32)]
+
+
+def merge_params(min_overlap=30, max_mismatch_pct=10, qual_base=33, qual_cap=41):
+    """an rc_merge_params; nothing is checked here: the library says what is out of range"""
+    return _MergeParams(int(min_overlap), int(max_mismatch_pct), int(qual_base), int(qual_cap))
+
+
+def merge_tally_dict(words):
+    """MERGE_TALLY_WORDS 64-bit words laid out as an rc_merge_tally (a copy of device memory, say) -> a dict named as the
+    struct's fields: ints and a numpy uint64 array"""
+    w = np.ascontiguousarray(words).view(np.uint64).reshape(-1)
+    if w.size != MERGE_TALLY_WORDS:
+        raise ValueError("an rc_merge_tally has %d 64-bit words, got %d" % (MERGE_TALLY_WORDS, w.size))
+    t = w.view(MERGE_TALLY_DTYPE)[0]
+    return {n: (int(t[n]) if t[n].shape == () else t[n].copy()) for n in MERGE_TALLY_DTYPE.names}
+
+
 class _DeviceBatch(C.Structure):
     _fields_ = [("mode", C.c_int), ("n_reads", C.c_uint32), ("nbytes", C.c_uint64),
                 ("max_read_len", C.c_int32),
@@ -329,6 +359,7 @@ def load_library():
     L.rc_mate_overlap_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp]
     L.rc_mate_overlap_begin.argtypes = [vp, C.c_int32, C.c_int32]
     L.rc_read_trim_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(_TrimParams), vp, vp, vp]
+    L.rc_read_merge_device.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint64, C.c_int32, C.c_int32, C.POINTER(_MergeParams), vp, vp, vp, vp, C.c_uint64, vp]
     L.rc_mate_overlap_get.argtypes = [vp, C.POINTER(_MateOverlap)]
     L.rc_mate_overlap_end.argtypes = [vp]
     L.rc_estimate_error_rate.argtypes = [vp, C.c_double, C.POINTER(C.c_double)]
@@ -679,6 +710,19 @@ class Context:
         p = trim_params() if params is None else params
         self._ck(self._L.rc_read_trim_device(self._h, _ptr(d_seq), _ptr(d_qual), _ptr(d_off), int(n_reads), int(nbytes), int(max_read_len), int(mode),
                                              C.byref(p), _ptr(d_out), _ptr(d_keep), _ptr(d_tally)))
+
+    # ---- read merging: overlapping mates into one read each, a new compact arena written on the device ----
+    def read_merge_device(self, d_seq, d_qual, d_off, n_reads, nbytes, max_read_len, mode, params, d_rows, d_mseq, d_mqual, d_moff, out_cap, d_tally=None):
+        """rc_read_merge_device: the pairs (mode 1: in halves, 2: interleaved) of an arena in HBM as they are, d_qual (may be None)
+        their quality bytes at the same offsets; params: merge_params(...) (None: the defaults); d_rows: device memory for
+        n_reads / 2 x 4 int32 (merged_len, d, v, m: READ_MERGE_DTYPE); the merged reads go to d_mseq, and their qualities to
+        d_mqual (may be None), out_cap >= nbytes bytes each on a 16-byte boundary, at the offsets d_moff (n_reads / 2 + 1 uint32;
+        the last is the new arena's size); an unmerged pair becomes an empty read.  The counts are ADDED to d_tally (may be
+        None): device memory for MERGE_TALLY_WORDS uint64, zeroed by the caller (merge_tally_dict reads a copy of it).  The new
+        arena is one every per-read entry point takes in mode 0.  Needs no table.  Asynchronous: sync() to wait."""
+        p = merge_params() if params is None else params
+        self._ck(self._L.rc_read_merge_device(self._h, _ptr(d_seq), _ptr(d_qual), _ptr(d_off), int(n_reads), int(nbytes), int(max_read_len), int(mode),
+                                              C.byref(p), _ptr(d_rows), _ptr(d_mseq), _ptr(d_mqual), _ptr(d_moff), int(out_cap), _ptr(d_tally)))
 
     # ---- per-read screen against a second k-mer set: valid and hit windows, covered bases, longest run of hits ----
     def read_screen_device(self, screen, d_seq, d_off, n_reads, nbytes, max_read_len, d_out, min_count=1):

@@ -451,6 +451,13 @@ int rc_launch_mate_overlap(rc_ctx *ctx, const uint8_t *d_before, const uint8_t *
 int rc_launch_read_trim(rc_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int max_read_len,
                         int mode, const void *params, void *d_out, uint8_t *d_keep, void *d_tally);
 
+// rc_merge.hip: the pairs of an arena (mode 1 or 2) merged into a new compact arena d_mseq / d_mqual (may be null) / d_moff
+// (n_reads / 2 + 1 entries), d_rows[u] = the rc_read_merge of unit u (rc_merge.h), the counts added to d_tally (an rc_merge_tally
+// in HBM, may be null); plan kernel, scan, write kernel on ctx's stream, scratch in ctx->sel_tmp; no table.  params: an
+// rc_merge_params that has been checked
+int rc_launch_read_merge(rc_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int max_read_len,
+                         int mode, const void *params, void *d_rows, uint8_t *d_mseq, uint8_t *d_mqual, uint32_t *d_moff, size_t out_cap, void *d_tally);
+
 // rc_dups.hip: one 128-bit key per unit of an arena (mode as rc_device_batch: n_reads units, or n_reads / 2 pairs) on stream st;
 // the census of n keys in HBM (left as they are) into host arrays copies[max_bin + 1], *distinct -- synchronous
 int rc_launch_read_keys(rc_ctx *ctx, hipStream_t st, const uint8_t *d_seq, size_t nbytes, const uint32_t *d_off, uint32_t n_reads, int mode,
