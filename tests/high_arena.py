@@ -167,6 +167,13 @@ def halves(x):
     return x[0:24:2] + x[24:38] + x[1:24:2] + x[38:]
 
 
+def split(x):
+    """a list that goes with trim_case's reads in the order of mode 1 with EVERY pair a pair again: all first mates, then all
+    second mates.  The last read is still the empty one; the reads in front of it are the tail's second mates."""
+    assert len(x) % 2 == 0
+    return x[0::2] + x[1::2]
+
+
 @functools.lru_cache(maxsize=None)
 def overlap_case():
     """the reads of trim_case as the bases as read, and a corrected version of them: every third read of 20 bases or more with
@@ -209,6 +216,29 @@ def correct_case():
 
 
 # ---- one filled arena: a base batch of about 1 MiB tiled up to 2^32 - 1 bytes -------------------------------------------------
+def _tiling(fixed, fillers):
+    """(reps, f, B): `reps` copies of a distinct list of `fixed` bytes (NULs counted, the filler pair's two included) and f filler
+    bases, f one of `fillers`, are a base batch of B bytes: about 1 MiB, an odd number, and such that whole copies of it leave 2 to
+    2 048 bytes of an arena of 2^32 - 1 -- the longest such rest on offer"""
+    pick = None
+    for reps in range(51, 141, 2):
+        for f in fillers:
+            B = reps * (fixed + f)
+            if B % 2 == 1 and 14 << 16 <= B <= 18 << 16 and 2 <= TOP_NBYTES % B <= 2048:
+                if pick is None or TOP_NBYTES % B > TOP_NBYTES % pick[2]:      # (the longest padding read on offer)
+                    pick = (reps, f, B)
+    assert pick is not None
+    return pick
+
+
+def _tiled_case(reads, quals, reps, B):
+    """the dict of a filled arena: the distinct list, its repeats, and the pair of N reads that takes the arena's last bytes"""
+    rem = TOP_NBYTES % B
+    tail = [b"N" * min(rem - 2, 1023), b"N" * (rem - 2 - min(rem - 2, 1023))]
+    assert sum(len(r) + 1 for r in reads) * reps == B and (TOP_NBYTES // B) * B + sum(len(r) + 1 for r in tail) == TOP_NBYTES
+    return dict(reads=reads, quals=quals, reps=reps, base_bytes=B, tiles=TOP_NBYTES // B, tail=tail, tail_quals=[b"I" * len(t) for t in tail])
+
+
 @functools.lru_cache(maxsize=None)
 def filled_case():
     """A list of distinct interleaved pairs -- 40 pairs of 37 to 250 bases cut from fragments (some overlap, some run into the
@@ -224,19 +254,61 @@ def filled_case():
         La, Lb = (37, 250) if i == 0 else (250, 37) if i == 1 else (int(x) for x in rng.integers(37, 251, 2))
         reads += tc.pair_of(rng, int(rng.integers(30, 400)), La, Lb, tail=tc.AD)
     reads += [tc.rand_seq(rng, L) for L in TAIL_LENGTHS]
-    fixed = sum(len(r) + 1 for r in reads) + 1                       # (+ 1: the filler pair's empty read)
-    pick = None
-    for reps in range(51, 141, 2):
-        for f in range(1024):
-            B = reps * (fixed + f + 1)
-            if B % 2 == 1 and 14 << 16 <= B <= 18 << 16 and 2 <= TOP_NBYTES % B <= 2048:
-                if pick is None or TOP_NBYTES % B > TOP_NBYTES % pick[2]:      # (the longest padding read on offer)
-                    pick = (reps, f, B)
-    assert pick is not None
-    reps, f, B = pick
+    reps, f, B = _tiling(sum(len(r) + 1 for r in reads) + 2, range(1024))      # (+ 2: the filler pair's NULs)
     reads += [tc.rand_seq(np.random.default_rng(f), f), b""]
     quals = [tc.rand_qual(rng, len(r), 2, 41) for r in reads]
-    rem = TOP_NBYTES % B
-    tail = [b"N" * min(rem - 2, 1023), b"N" * (rem - 2 - min(rem - 2, 1023))]
-    assert sum(len(r) + 1 for r in reads) * reps == B and (TOP_NBYTES // B) * B + sum(len(r) + 1 for r in tail) == TOP_NBYTES
-    return dict(reads=reads, quals=quals, reps=reps, base_bytes=B, tiles=TOP_NBYTES // B, tail=tail, tail_quals=[b"I" * len(t) for t in tail])
+    return _tiled_case(reads, quals, reps, B)
+
+
+# ---- merging: the trimming batch with its qualities, and a filled arena most of which comes back out ---------------------------
+@functools.lru_cache(maxsize=None)
+def merge_case():
+    """trim_case's reads and qualities as the pairs read_merge_device merges: (reads, quals, params).  The last pairs of `top`:
+    1022 and 150 bases merge to 1100 (the wide instance), 16 and 15 to a read-through fragment of 13, 1 and 0 not at all."""
+    import merge_model as mm
+    reads, quals, _ = trim_case()
+    return reads, quals, mm.params(min_overlap=12)
+
+
+def _noisy(rng, a):
+    """a with up to two of its bases substituted, as tests/test_read_merge.py's _noisy does"""
+    a = bytearray(a)
+    for j in set(rng.integers(0, len(a), int(rng.integers(0, 3))).tolist()):
+        a[j] = b"ACGT"[(b"ACGT".index(a[j]) + 1) % 4]
+    return bytes(a)
+
+
+MERGE_FILLER_OVERLAP = (40, 41)     # the filler pair's mates overlap by one of these: the one that makes the merged byte count odd
+
+
+@functools.lru_cache(maxsize=None)
+def merge_filled_case():
+    """filled_case's shape for read_merge_device: 40 distinct interleaved pairs of 150 to 250 bases, most of them cut from a
+    fragment 30 to 45 bases shorter than the mates together (they merge, and most of the input comes back out), one in eight from
+    a fragment of 30 to 140 bases with the adapter behind it (read-through), one in eight from a fragment too long to overlap;
+    mate 1 with up to four bases substituted (_noisy, twice), so that the qualities decide bases.  Behind them the reads of
+    TAIL_LENGTHS, a filler pair, `reps` copies and the pair of N reads, as in filled_case.  The filler pair merges: its length
+    makes the base batch's byte count odd, its overlap the base batch's MERGED byte count (`base_out`), so every copy's input and
+    output have another alignment modulo 16.  `want`: merge_model's (rows, moff, mseq, mqual, tally) of the distinct list in
+    mode 2, `tail_want` those of the N pair; `params` the model's defaults."""
+    import merge_model as mm
+    import trim_cases as tc
+    rng = np.random.default_rng(2147483647)
+    p = mm.params()
+    reads = []
+    for i in range(40):
+        La, Lb = (int(x) for x in rng.integers(150, 251, 2))
+        F = int(rng.integers(30, 141)) if i % 8 == 3 else La + Lb + int(rng.integers(20, 200)) if i % 8 == 6 else La + Lb - int(rng.integers(30, 46))
+        a, b = tc.pair_of(rng, F, La, Lb, tail=tc.AD)
+        reads += [_noisy(rng, _noisy(rng, a)), b]
+    reads += [tc.rand_seq(rng, L) for L in TAIL_LENGTHS]
+    quals = [tc.rand_qual(rng, len(r), 2, 41) for r in reads]
+    reps, f, B = _tiling(sum(len(r) + 1 for r in reads) + 2, range(200, 1024))
+    out_fixed = int(mm.merge_batch(reads, quals, 2, p)[1][-1])
+    ov = [v for v in MERGE_FILLER_OVERLAP if (out_fixed + f - v + 1) % 2 == 1][0]       # (the filler merges to f - ov bases and a NUL)
+    reads += list(tc.pair_of(np.random.default_rng(f), f - ov, f - f // 2, f // 2))
+    quals += [tc.rand_qual(rng, len(r), 2, 41) for r in reads[-2:]]
+    c = _tiled_case(reads, quals, reps, B)
+    want = mm.merge_batch(reads, quals, 2, p)
+    assert want[0][-1].tolist() == [f - ov, f - f // 2 - ov, ov, 0] and int(want[1][-1]) == out_fixed + f - ov + 1
+    return dict(c, params=p, want=want, base_out=reps * int(want[1][-1]), tail_want=mm.merge_batch(c["tail"], c["tail_quals"], 2, p))

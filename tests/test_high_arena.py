@@ -4,7 +4,11 @@ Every test places a small batch (tests/high_arena.py) where the uint32 offsets a
 at lead 0, 5 and 15; the `top` window up to byte 2^32 - 2, at every lead 0..15 -- and compares every output row, key and tally
 word with the CPU reference the entry point's own test file compares with, run on the reads as byte strings: the reference never
 sees an offset.  The arenas are two uninitialised 4 GiB allocations shared by the module; only the window is written.
-tests/test_high_arena_cases.py shows on the CPU that the expected results are not empty ones."""
+tests/test_high_arena_cases.py shows on the CPU that the expected results are not empty ones.
+
+read_merge_device, the one entry point that writes an arena and an offset array, has its high-offset coverage here too (section 7):
+both modes at every placement with qualities and two more 4 GiB arenas for its output, and one filled arena whose merged output
+passes 2^31, handed on to read_trim_device as it lies in HBM.  tests/test_read_merge.py keeps the contract at small offsets."""
 import functools
 
 import numpy as np
@@ -12,6 +16,7 @@ import pytest
 
 import datasets
 import high_arena as ha
+import merge_model as mm
 import recur_model as rm
 import rcorrector_amd
 import test_mate_overlap_host as mho
@@ -21,6 +26,9 @@ from rcorrector_amd import binding as B
 from test_duplicates import dup_key, host_keys  # noqa: F401  (dup_key: the fixture that builds the host program)
 from test_read_depth import restate_all as depth_rows
 from test_read_depth import table_of
+from test_read_merge import POISON
+from test_read_merge import assert_equal as assert_merge_equal
+from test_read_merge import params_of as merge_params_of
 from test_read_screen import restate_all as screen_rows
 from test_read_trim import params_of
 from test_weak_profile import restate_all as weak_rows
@@ -339,6 +347,37 @@ def fill(buf, lead, c, strings, tail):
     return buf.data_ptr() + lead
 
 
+def filled_offsets(c):
+    """(n, d_off) of a filled arena (ha.filled_case, ha.merge_filled_case): the offsets of every copy of the distinct list and of
+    the tail pair, made on the device, as the uint32 bit patterns in an int32 tensor of n + 1"""
+    import torch
+    T, BB, copies = c["tiles"], c["base_bytes"], c["tiles"] * c["reps"]
+    n = copies * len(c["reads"]) + 2
+    lens1 = np.array([len(r) + 1 for r in c["reads"]], dtype=np.int64)
+    one_off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens1)[:-1]])).cuda()
+    off = (torch.arange(copies, dtype=torch.int64, device="cuda")[:, None] * int(lens1.sum()) + one_off[None, :]).reshape(-1)
+    off = torch.cat([off, torch.tensor([T * BB, T * BB + len(c["tail"][0]) + 1, ha.TOP_NBYTES], dtype=torch.int64, device="cuda")])
+    assert off.numel() == n + 1 and int(off[-3]) == T * BB > 0xFFFFF000 and bool((off[1:] > off[:-1]).all())
+    t_off = uint32_bits(off)
+    assert bool((t_off.to(torch.int64) & 0xFFFFFFFF == off).all())
+    return n, t_off
+
+
+def uint32_bits(x):
+    """an int64 tensor of values below 2^32 as their uint32 bit patterns in an int32 tensor"""
+    import torch
+    return torch.where(x >= 1 << 31, x - (1 << 32), x).to(torch.int32)
+
+
+def assert_tiled(copies, got, want, tail_want, what):
+    """the device tensor `got` is `copies` times the model's `want` of the distinct list, then `tail_want`"""
+    import torch
+    w = torch.from_numpy(np.ascontiguousarray(want)).cuda()
+    body = got[:copies * len(want)].view((copies,) + tuple(w.shape))
+    assert torch.equal(body, w.expand_as(body)), "%s: a tile differs from the base batch" % what
+    assert np.array_equal(got[copies * len(want):].cpu().numpy(), tail_want), "%s: the tail" % what
+
+
 def test_one_filled_arena(arenas):
     """nbytes = 2^32 - 1, 27.6 million reads: read_trim_device in mode 2 and read_depth_device at lead 5, every tile's rows equal to
     the base batch's, the tally tiles x the base batch's + the tail's; then, at lead 0, rc_probe_device byte for byte, the counter
@@ -346,17 +385,8 @@ def test_one_filled_arena(arenas):
     import torch
     from test_read_screen import counts_of_reads
     c = ha.filled_case()
-    reads, quals, T, R, BB = c["reads"], c["quals"], c["tiles"], c["reps"], c["base_bytes"]
-    nd, copies = len(reads), T * R
-    n = copies * nd + 2
-    lens1 = np.array([len(r) + 1 for r in reads], dtype=np.int64)
-    one_off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens1)[:-1]])).cuda()
-    off = (torch.arange(copies, dtype=torch.int64, device="cuda")[:, None] * int(lens1.sum()) + one_off[None, :]).reshape(-1)
-    off = torch.cat([off, torch.tensor([T * BB, T * BB + len(c["tail"][0]) + 1, ha.TOP_NBYTES], dtype=torch.int64, device="cuda")])
-    assert off.numel() == n + 1 and int(off[-3]) == T * BB > 0xFFFFF000 and bool((off[1:] > off[:-1]).all())
-    t_off = torch.where(off >= 1 << 31, off - (1 << 32), off).to(torch.int32)      # the uint32 bit patterns
-    assert bool((t_off.to(torch.int64) & 0xFFFFFFFF == off).all())
-    del off
+    reads, quals, copies = c["reads"], c["quals"], c["tiles"] * c["reps"]
+    n, t_off = filled_offsets(c)
     p = tm.params()
     rows, keep, tally = tm.trim_batch(reads, quals, 2, p)
     t_rows, t_keep, t_tally = tm.trim_batch(c["tail"], c["tail_quals"], 2, p)
@@ -368,10 +398,7 @@ def test_one_filled_arena(arenas):
     table_of(ctx, counts)
 
     def tiled(got, want, tail_want, what):
-        w = torch.from_numpy(np.ascontiguousarray(want)).cuda()
-        body = got[:copies * len(want)].view((copies,) + tuple(w.shape))
-        assert torch.equal(body, w.expand_as(body)), "%s: a tile differs from the base batch" % what
-        assert np.array_equal(got[copies * len(want):].cpu().numpy(), tail_want), "%s: the tail" % what
+        assert_tiled(copies, got, want, tail_want, what)
 
     # trim and depth, the arena 5 bytes behind a 16-byte boundary
     ps, pq = fill(arenas[0], 5, c, reads, c["tail"]), fill(arenas[1], 5, c, quals, c["tail_quals"])
@@ -419,3 +446,155 @@ def test_one_filled_arena(arenas):
     assert np.array_equal(codes[order], want_codes)
     assert np.array_equal(cnt[order].astype(np.int64), np.array([counts[int(x)] for x in want_codes], dtype=np.int64) * copies)
     counter.close()
+
+
+# ---- 7. merging: the one entry point that writes an arena and an offset array, so the offsets are large on the way out too -------
+ARENA_ALLOC = (ha.TOP_NBYTES + 16 + 15) // 16 * 16          # what ha.allocate() takes
+MERGE_GUARD = 4096                                          # bytes behind d_moff[units] that must stay poison
+
+
+def merge_need_free():
+    """device bytes test_one_filled_arena_merged takes at its peak: the four arenas; per read the offsets (int32, and the int64
+    ones with two temporaries while they are made); per unit the merge's rows, d_moff and the library's scratch lengths, the
+    hand-off's rows and keep flags, and the expected d_moff (int64, with a temporary); and one byte for every output byte looked
+    at in one comparison, which is at most an arena"""
+    c = ha.merge_filled_case()
+    n = c["tiles"] * c["reps"] * len(c["reads"]) + 2
+    return 4 * ARENA_ALLOC + n * (4 + 3 * 8) + (n // 2) * (16 + 4 + 4 + 16 + 1 + 2 * 8) + ARENA_ALLOC
+
+
+@pytest.fixture(scope="module")
+def merged_arenas(arenas):
+    """two more 4 GiB allocations: the merged sequences and the merged qualities (out_cap is at least nbytes)"""
+    import torch
+    torch.cuda.empty_cache()
+    free, need = torch.cuda.mem_get_info()[0], merge_need_free() - sum(a.numel() for a in arenas)       # (the input arenas are there already)
+    if free < need:
+        pytest.skip("%.1f GiB of device memory are free, the merged arenas above 2 GiB need %.1f more" % (free / 2.0 ** 30, need / 2.0 ** 30))
+    bufs = [ha.allocate(), ha.allocate()]
+    yield bufs
+    del bufs[:]
+    torch.cuda.empty_cache()
+
+
+@functools.lru_cache(maxsize=None)
+def merge_runs(mode):
+    """[(reads, quals, the windows with their leads, merge_model's results)]: mode 2 as trimming runs; mode 1 through halves()
+    as trimming runs, and through split() -- every pair a pair again, so the expected results are mode 2's -- up to the arena's last byte"""
+    reads, quals, p = ha.merge_case()
+    if mode == 2:
+        return [(reads, quals, ha.windows(reads, ha.TRIM_MID), mm.merge_batch(reads, quals, 2, p))]
+    h, hq, s, sq = ha.halves(reads), ha.halves(quals), ha.split(reads), ha.split(quals)
+    return [(h, hq, ha.windows(h, ha.TRIM_MID_HALVES), mm.merge_batch(h, hq, 1, p)),
+            (s, sq, [(ha.top_plain(s), ha.TOP_LEADS)], mm.merge_batch(s, sq, 1, p))]
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_read_merge_device(arenas, merged_arenas, bare, mode):
+    """sequences and qualities at the same lead, d_mqual asked for, out_cap = nbytes; the rows, d_moff, both merged arenas and the
+    tally equal the model, and the 4096 bytes behind d_moff[units] are still poison"""
+    import torch
+    p = ha.merge_case()[2]
+    failures = []
+    for reads, quals, wins, want in merge_runs(mode):
+        n, units = len(reads), len(reads) // 2
+        total = int(want[1][units])
+        for w, leads in wins:
+            for lead in leads:
+                ps, pq, t_off = ha.put(arenas[0], lead, w), ha.put(arenas[1], lead, w, quals), ha.off_tensor(w)
+                for o in merged_arenas:
+                    o[:total + MERGE_GUARD] = POISON
+                rows = torch.full((units, 4), -7, dtype=torch.int32, device="cuda")
+                moff = torch.full((units + 2,), -7, dtype=torch.int32, device="cuda")
+                tal = torch.zeros(B.MERGE_TALLY_WORDS, dtype=torch.int64, device="cuda")
+                torch.cuda.synchronize()
+                try:
+                    bare.read_merge_device(ps, pq, t_off, n, w["nbytes"], 1023, mode, merge_params_of(p), rows, merged_arenas[0], merged_arenas[1], moff,
+                                           w["nbytes"], tal)
+                    bare.sync()
+                    m = moff.cpu().numpy()
+                    got = {"rows": rows.cpu().numpy(), "moff": m.view(np.uint32)[:units + 1], "tally": B.merge_tally_dict(tal.cpu().numpy()),
+                           "mseq": merged_arenas[0][:total].cpu().numpy().tobytes(), "mqual": merged_arenas[1][:total].cpu().numpy().tobytes()}
+                    assert m[units + 1] == -7, "d_moff has units + 1 entries"
+                    assert_merge_equal(got, want)
+                    for o, what in zip(merged_arenas, ("mseq", "mqual")):
+                        assert bool((o[total:total + MERGE_GUARD] == POISON).all()), "%s: a byte behind d_moff[units] = %d was written" % (what, total)
+                except (AssertionError, rcorrector_amd.RcorrectorError) as e:      # (a refusal is one placement's failure: the others still run)
+                    failures.append("%s: %s" % (where(w, lead), (str(e) or repr(e)).splitlines()[0]))
+    report(failures)
+
+
+def test_one_filled_arena_merged(arenas, merged_arenas, bare):
+    """nbytes = 2^32 - 1, 21.8 million reads in interleaved pairs with qualities at lead 5, most of which merge: the merged arenas
+    take 2.66 GiB, so d_moff passes 2^31 and every copy of the distinct list lands on another alignment modulo 16.  Every copy's
+    rows, d_moff (as uint32 bit patterns) and merged bytes equal merge_model's of the distinct list, the tally is copies x the
+    list's + the tail pair's, every byte at or behind d_moff[units] is still poison.  Then the merged arenas, as they lie in HBM,
+    go to read_trim_device in mode 0: d_moff above 2^31 as an input offset array.
+    Measured on an MI355X in one session: d_moff[units] = 2 859 060 727; 0.19 s for this test's call (and 1.3 s to set up its
+    fixture: the model on the distinct list, two allocations) against 3.09 s for test_one_filled_arena's call, so nothing of it
+    had to be dropped."""
+    import torch
+    c = ha.merge_filled_case()
+    reads, quals = c["reads"], c["quals"]
+    copies, ndu = c["tiles"] * c["reps"], len(reads) // 2
+    rows, moff, mseq, mqual, tally = c["want"]
+    t_rows, t_moff, t_mseq, t_mqual, t_tally = c["tail_want"]
+    per = int(moff[ndu])
+    assert per * c["reps"] == c["base_out"] and t_mseq == t_mqual == b"\0"
+    total = copies * per + 1
+    n, t_off = filled_offsets(c)
+    units = n // 2
+    assert units == copies * ndu + 1
+    ps, pq = fill(arenas[0], 5, c, reads, c["tail"]), fill(arenas[1], 5, c, quals, c["tail_quals"])
+    for o in merged_arenas:
+        o.fill_(POISON)
+    d_rows = torch.full((units, 4), -7, dtype=torch.int32, device="cuda")
+    d_moff = torch.full((units + 1,), -7, dtype=torch.int32, device="cuda")
+    d_tally = torch.zeros(B.MERGE_TALLY_WORDS, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    bare.read_merge_device(ps, pq, t_off, n, ha.TOP_NBYTES, 1023, 2, merge_params_of(c["params"]), d_rows, merged_arenas[0], merged_arenas[1], d_moff,
+                           ha.TOP_NBYTES, d_tally)
+    bare.sync()
+    del t_off
+    got_total = int(d_moff[units].item()) & 0xFFFFFFFF
+    print("d_moff[units] = %d" % got_total)
+    assert got_total > (1 << 31) + (1 << 29), "the merged arena does not reach 2^31 + 2^29: d_moff[units] = %d" % got_total
+    assert_tiled(copies, d_rows, rows, t_rows, "merge rows")
+    want_moff = (torch.arange(copies, dtype=torch.int64, device="cuda")[:, None] * per + torch.from_numpy(moff[:ndu].astype(np.int64)).cuda()[None, :]).reshape(-1)
+    want_moff = uint32_bits(torch.cat([want_moff, torch.tensor([copies * per, total], dtype=torch.int64, device="cuda")]))
+    bad = torch.nonzero(d_moff != want_moff)
+    assert bad.numel() == 0, "d_moff differs at %d units, first at unit %d" % (bad.numel(), int(bad[0]))
+    del want_moff, bad
+    assert got_total == total
+    for o, base, what in zip(merged_arenas, (mseq, mqual), ("mseq", "mqual")):
+        w = torch.from_numpy(np.frombuffer(base, dtype=np.uint8).copy()).cuda()
+        body = o[:copies * per].view(copies, per)
+        assert torch.equal(body, w.expand_as(body)), "%s: a copy's merged bytes differ from the distinct list's" % what
+        assert int(o[total - 1]) == 0, "%s: the tail pair's NUL" % what
+        assert bool((o[total:] == POISON).all()), "%s: a byte at or behind d_moff[units] = %d was written" % (what, total)
+    got = B.merge_tally_dict(d_tally.cpu().numpy())
+    for f in mm.TALLY_KEYS:
+        want = np.asarray(tally[f], np.uint64) * np.uint64(copies) + np.asarray(t_tally[f], np.uint64)
+        assert np.array_equal(np.asarray(got[f], np.uint64), want), "merge tally %s" % f
+    del d_rows
+
+    # the hand-off: the merged reads as single reads, where the merge left them
+    p = tm.params()
+    strings = [mseq[moff[u]:moff[u + 1] - 1] for u in range(ndu)]
+    qstrings = [mqual[moff[u]:moff[u + 1] - 1] for u in range(ndu)]
+    assert max(len(s) for s in strings) <= 1023 and all(len(s) == r[0] for s, r in zip(strings, rows))
+    h_rows, h_keep, h_tally = tm.trim_batch(strings, qstrings, 0, p)
+    ht_rows, ht_keep, ht_tally = tm.trim_batch([b""], [b""], 0, p)
+    assert (h_rows[:, 0] < rows[:, 0]).sum() > 3 and 0 < h_tally["units_kept"] < h_tally["units"]       # (some merged reads are cut, some units are short)
+    d_out = torch.full((units, 4), -7, dtype=torch.int32, device="cuda")
+    d_keep = torch.full((units,), 9, dtype=torch.uint8, device="cuda")
+    d_tally = torch.zeros(B_TALLY, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    bare.read_trim_device(merged_arenas[0], merged_arenas[1], d_moff, units, total, 1023, 0, params_of(p), d_out, d_keep, d_tally)
+    bare.sync()
+    assert_tiled(copies, d_out, h_rows, ht_rows, "hand-off: trim rows")
+    assert_tiled(copies, d_keep, h_keep, ht_keep, "hand-off: trim keep")
+    got = B.trim_tally_dict(d_tally.cpu().numpy())
+    for f in tm.empty_tally():
+        want = np.asarray(h_tally[f], np.uint64) * np.uint64(copies) + np.asarray(ht_tally[f], np.uint64)
+        assert np.array_equal(np.asarray(got[f], np.uint64), want), "hand-off: trim tally %s" % f

@@ -3,7 +3,9 @@ tests/merge_cases.py, each named by the edge it hits: the rows, d_moff, both out
 tests/merge_model.py exactly, and every byte of the output arenas at or behind d_moff[units] is still the poison they were filled
 with.  Then the input arena's alignment, the output offsets' residues, the grid-stride wrap, the calls that do nothing or are
 refused, the offset shared with read_trim and the mate-overlap report, the merged arena handed on to read_depth_device, and an
-input arena across byte 2^31."""
+input arena across byte 2^31.  The rest of the high offsets -- both modes and the quality arenas up to byte 2^32 - 2, a merged
+arena and d_moff past 2^31, and that arena handed on -- are in tests/test_high_arena.py (test_read_merge_device,
+test_one_filled_arena_merged)."""
 import ctypes
 
 import numpy as np
