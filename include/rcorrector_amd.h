@@ -696,7 +696,8 @@ int rc_read_trim_device(rc_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual
  *   d_qual == NULL (FASTA)    a disagreement keeps mate 1's base and counts as a tie; no quality arena is written
  * A mate has at most 1023 bases; a merged read may have up to La + Lb - min_overlap <= 2045.  Of a read longer than 1023 bases
  * rc_read_trim_device and rc_mate_overlap_device look only at the first 1023; the entry points that stage reads in the probe tile
- * (rc_read_depth_device, rc_read_screen_device, rc_weak_profile_device) take it as no read: four zeros.  Not in scope: merging inside rcorrector, a slot-transport registration,
+ * (rc_read_depth_device, rc_read_screen_device) take it as no read: four zeros; rc_weak_profile_device, whose reduce walks a read
+ * of any length, profiles all of it; rc_trust_profile_device counts its first windows; rc_correct_device refuses the batch.  Not in scope: merging inside rcorrector, a slot-transport registration,
  * a compacted trimmed arena, indel-tolerant overlap, posterior-probability quality models.  No byte parity with FLASH, PEAR or
  * fastp is claimed.  No reference counterpart. */
 #define RC_MERGE_LEN_BINS 2048
@@ -911,7 +912,8 @@ typedef struct {
 int rc_correct_batch_traced(rc_ctx *ctx, rc_batch *b, rc_trace *t);
 
 /* Batch already resident in HBM (asynchronous on the context's stream; rc_sync() to wait).
- * In mode 1 the arena holds the n/2 first mates followed by the n/2 second mates. */
+ * In mode 1 the arena holds the n/2 first mates followed by the n/2 second mates.  max_read_len above 1023 (utils.h:7; a merged
+ * arena may hold such reads) is RC_STATUS_ARG, refused before anything is launched: no read of the arena is corrected. */
 typedef struct {
     int mode;
     uint32_t n_reads;

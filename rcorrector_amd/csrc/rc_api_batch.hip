@@ -33,6 +33,12 @@ int rc_correct_check(rc_ctx *ctx, const rc_device_batch *b)
         rc_set_error(ctx, "correct_device: arena of %llu bytes exceeds the 4 GiB batch limit", (unsigned long long)b->nbytes);
         return RC_ERR_ARG;
     }
+    // fill_args refuses such a batch too, but only when a kernel is launched with the batch's own max_len: in a tiered batch
+    // that is the long tier's pass, after the short and the middle tier have been corrected in place
+    if (b->max_read_len >= RC_MAX_READ_LENGTH) {
+        rc_set_error(ctx, "correct: read of %d bases exceeds the %d-base limit (utils.h:7)", b->max_read_len, RC_MAX_READ_LENGTH - 1);
+        return RC_ERR_ARG;
+    }
     if (!ctx->d_buckets) {  // (before anything is launched: every probe kernel dereferences the table)
         rc_set_error(ctx, "correct: no k-mer table loaded");
         return RC_ERR_STATE;
