@@ -954,7 +954,9 @@ int rc_probe_device(rc_ctx *ctx, const uint8_t *d_seq, uint64_t nbytes, int32_t 
 int rc_sync(rc_ctx *ctx);
 
 /* ---- measurement ----------------------------------------------------------------------------- */
-/* with profiling on, every kernel launch is bracketed by HIP events on the context's stream */
+/* with profiling on, every kernel launch is bracketed by HIP events on the stream it runs on.  The events are only recorded
+ * when the kernel is launched: no launch waits for the GPU, and the pairs are waited for and added up by rc_profile_get and
+ * rc_sync (or when the context's small pool of pairs is full). */
 int rc_profile_enable(rc_ctx *ctx, int on);
 /* on = 2 additionally runs the instrumented build of the correction kernel (slower; same results),
  * which counts, over the launches since the last reset: the reads the threshold kernel could not
@@ -969,7 +971,11 @@ int rc_profile_correct_counters(rc_ctx *ctx, uint64_t *reads_listed, uint64_t *g
 int rc_profile_read_rounds(rc_ctx *ctx, int32_t *d_rounds);
 /* kernel 0 = probe, 1 = threshold, 2 = correct, 3 = isolated substitutions, 4 = weak-k-mer profile, 5 = the trust profile's
  * planes, 6 = its accumulate and column sums, 7 = per-read k-mer depth, 8 = per-read screen against a second k-mer set,
- * 9 = normalisation's unit selection; accumulated since the last reset */
+ * 9 = normalisation's unit selection; accumulated since the last reset (the call waits for the launches still in flight).
+ * Where rc_correct_device runs a batch as a chunked pipeline (RC_PIPELINE_CHUNKS), kernels 0, 2 and 3 are
+ * launched once per chunk on two streams and each kind is timed ONCE per call, from its first chunk's launch to the end of
+ * its last: `launches` still counts arenas, and the three figures are spans that overlap in time -- their sum exceeds the
+ * time of the step, and a span includes what its stream waited for. */
 int rc_profile_get(rc_ctx *ctx, int kernel, double *total_ms, uint64_t *launches);
 int rc_profile_reset(rc_ctx *ctx);
 

@@ -58,9 +58,16 @@ void rc_table_release(rc_ctx *ctx)
 int rc_drain(rc_ctx *ctx)
 {
     RC_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    // (a batch's follower stream is joined into `stream` before the batch's last kernel: stream2 has something of its own only
+    // after a call that failed between fork and join)
     RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (rc_ctx *ln : ctx->lane)
-        if (ln) RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream));
+    RC_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream2));
+    rc_timer_resolve(ctx);
+    for (rc_ctx *ln : ctx->lane) {
+        if (!ln) continue;
+        RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream));
+        RC_CHECK_HIP(ctx, hipStreamSynchronize(ln->stream2));
+    }
     return RC_OK;
 }
 
@@ -138,18 +145,38 @@ rc_table_view rc_view(const rc_ctx *ctx)
 
 void rc_timer_begin(rc_ctx *ctx)
 {
-    if (ctx->profile) (void)hipEventRecord(ctx->ev0, ctx->stream);
+    if (!ctx->profile) return;
+    if (ctx->timer_anon >= 0)  // (a launcher that starts its timer twice)
+        ctx->timers.rebegin(ctx->timer_anon, ctx->stream);
+    else
+        ctx->timer_anon = ctx->timers.begin(ctx->stream);
 }
 
 void rc_timer_end(rc_ctx *ctx, int which)
 {
-    if (!ctx->profile) return;
-    (void)hipEventRecord(ctx->ev1, ctx->stream);
-    (void)hipEventSynchronize(ctx->ev1);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
-    ctx->timers[which].ms += ms;
-    ctx->timers[which].launches += 1;
+    if (ctx->timer_anon >= 0) ctx->timers.end(ctx->timer_anon, which, ctx->stream);
+    ctx->timer_anon = -1;
+}
+
+void rc_timer_begin_on(rc_ctx *ctx, int which, hipStream_t st, bool first)
+{
+    if (!ctx->profile || !first) return;
+    if (ctx->timer_open[which] >= 0)  // (a call that failed between its first and its last chunk left it open)
+        ctx->timers.rebegin(ctx->timer_open[which], st);
+    else
+        ctx->timer_open[which] = ctx->timers.begin(st);
+}
+
+void rc_timer_end_on(rc_ctx *ctx, int which, hipStream_t st, bool last)
+{
+    if (!last) return;
+    if (ctx->timer_open[which] >= 0) ctx->timers.end(ctx->timer_open[which], which, st);
+    ctx->timer_open[which] = -1;
+}
+
+void rc_timer_resolve(rc_ctx *ctx)
+{
+    ctx->timers.resolve();
 }
 
 void rc_lane_error(rc_ctx *ctx, const rc_ctx *lane)
@@ -244,9 +271,12 @@ rc_ctx *rc_create(const rc_config *cfg, char *errbuf, size_t errbuf_len)
     ctx->P.flags = 0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess) ctx->n_cu = prop.multiProcessorCount;
-    if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess ||
-        hipMalloc(&ctx->work.p, RC_WORK_BYTES) != hipSuccess) {
+    for (int &t : ctx->timer_open) t = -1;
+    bool made = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) == hipSuccess &&
+                hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking) == hipSuccess &&
+                hipEventCreateWithFlags(&ctx->pipe_join, hipEventDisableTiming) == hipSuccess;
+    for (hipEvent_t &e : ctx->pipe_ev) made = made && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+    if (!made || hipMalloc(&ctx->work.p, RC_WORK_BYTES) != hipSuccess) {
         delete ctx;
         return fail("rc_create: could not create stream/events");
     }
@@ -266,6 +296,8 @@ rc_ctx *rc_create(const rc_config *cfg, char *errbuf, size_t errbuf_len)
     if (const char *xo = getenv("RC_FUSED_XCD")) ctx->env_fused_xcd = atoi(xo) != 0;
     if (const char *qd = getenv("RC_PROBE_QUAD")) ctx->env_quad = atoi(qd) != 0 ? 1 : 0;
     if (const char *kl = getenv("RC_K3_LOCAL")) ctx->env_k3_local = atoi(kl) != 0;
+    if (const char *pc = getenv("RC_PIPELINE_CHUNKS")) ctx->env_pipe_chunks = atoi(pc) > 0 ? atoi(pc) : 0;
+    if (const char *pg = getenv("RC_PIPELINE_GRID_DIV")) ctx->env_pipe_grid_div = atoi(pg) > 0 ? atoi(pg) : 0;
     if (const char *wt = getenv("RC_FUSED_WAVE_TILES")) ctx->env_wave_tiles = atoi(wt) != 0;
     ctx->env_no_tier = getenv("RC_NO_TIER") != nullptr;
     if (const char *e = getenv("RC_FORCE_EC")) {
@@ -294,6 +326,7 @@ void rc_destroy(rc_ctx *c)
     }
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     rc_dbuf *bufs[] = {&ctx->counts, &ctx->strong, &ctx->info, &ctx->stack, &ctx->work,
                        &ctx->h_seq, &ctx->h_qual, &ctx->h_off, &ctx->h_res, &ctx->trace, &ctx->cls, &ctx->worklist, &ctx->sel_tmp,
                        &ctx->loc_a, &ctx->loc_list, &ctx->loc_span, &ctx->tier_flag, &ctx->tier_list, &ctx->cand, &ctx->single_list, &ctx->runs, &ctx->bs_dev, &ctx->weak_planes, &ctx->trust_planes, &ctx->trust_part};
@@ -332,8 +365,11 @@ void rc_destroy(rc_ctx *c)
     if (ctx->ovl_acc) (void)hipFree(ctx->ovl_acc);      // (the mate-overlap report's counts)
     rc_recur_release(ctx);                               // (the recurrence census's keys)
     rc_table_release(ctx);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+    ctx->timers.release();
+    for (hipEvent_t e : ctx->pipe_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (ctx->pipe_join) (void)hipEventDestroy(ctx->pipe_join);
+    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -392,12 +428,16 @@ int rc_profile_enable(rc_ctx *ctx, int on)
 int rc_profile_get(rc_ctx *ctx, int kernel, double *total_ms, uint64_t *launches)
 {
     if (!ctx || kernel < 0 || kernel >= RC_T_COUNT) return RC_ERR_ARG;
-    double ms = ctx->timers[kernel].ms;
-    uint64_t n = ctx->timers[kernel].launches;
+    // the pairs still pending are waited for here (no kernel is waited for when it is launched: rc_timer_pool.h)
+    (void)hipSetDevice(ctx->device);
+    rc_timer_resolve(ctx);
+    double ms = ctx->timers.total[kernel].ms;
+    uint64_t n = ctx->timers.total[kernel].launches;
     for (rc_ctx *ln : ctx->lane) {  // (the batches of slots > 0 ran in lane contexts)
         if (!ln) continue;
-        ms += ln->timers[kernel].ms;
-        n += ln->timers[kernel].launches;
+        rc_timer_resolve(ln);
+        ms += ln->timers.total[kernel].ms;
+        n += ln->timers.total[kernel].launches;
     }
     if (total_ms) *total_ms = ms;
     if (launches) *launches = n;
@@ -407,11 +447,15 @@ int rc_profile_get(rc_ctx *ctx, int kernel, double *total_ms, uint64_t *launches
 int rc_profile_reset(rc_ctx *ctx)
 {
     if (!ctx) return RC_ERR_ARG;
-    for (auto &t : ctx->timers) t = rc_kernel_timer();
+    ctx->timers.reset();
+    for (int &t : ctx->timer_open) t = -1;
+    ctx->timer_anon = -1;
     ctx->k3_listed = ctx->k3_rounds = ctx->k3_requests = 0;
     for (rc_ctx *ln : ctx->lane) {
         if (!ln) continue;
-        for (auto &t : ln->timers) t = rc_kernel_timer();
+        ln->timers.reset();
+        for (int &t : ln->timer_open) t = -1;
+        ln->timer_anon = -1;
         ln->k3_listed = ln->k3_rounds = ln->k3_requests = 0;
     }
     return RC_OK;

@@ -52,6 +52,109 @@ int rc_correct_check(rc_ctx *ctx, const rc_device_batch *b)
     return RC_OK;
 }
 
+// ---- the chunked pipeline ---------------------------------------------------------------------------------------------------
+// A whole, locality-ordered batch whose reads fit the fused probe + threshold kernel, cut into C chunks of whole tiles of the
+// locality list: the fused kernel is launched once per chunk on ctx->stream, and behind each launch the follower stream
+// (ctx->stream2) runs that chunk's compaction of the candidates, k_single, compaction of the classes and k_correct -- while the
+// fused kernel of the next chunks runs.  The fused kernel waits for memory (its probes) most of its life, k_single and k_correct
+// for their vector units.  *ran = false and nothing launched: the batch does not qualify, the caller runs it whole.
+//
+// What makes the two streams independent between a chunk's fork and the join:
+//  * a unit's mates share a tile, hence a chunk: the threshold exchange inside the fused kernel, k_single's and k_correct's
+//    strong[mate] / info[mate] never leave the chunk;
+//  * the fused kernel of chunk c' WRITES, of per-read state, only that of chunk c''s reads: counts (the reads' own k-mer positions;
+//    the up to three words it writes in front of and behind them are positions that hold no count, of any read), strong, info,
+//    cls, cand, runs, ret / l / m / h -- and READS the bases of its own reads only (rc_tile_copy_reads loads whole dwords and masks
+//    the neighbours' bytes, which k_single / k_correct of another chunk may be rewriting: never used);
+//  * the follower's kernels read and write the per-read state of chunk c's reads (c < c'), and what they share among themselves
+//    -- the two lists, their counters, the queue heads and phase counters in ctx->work, the search stack, the gathered flags --
+//    is used by one follower step at a time: stream2 is serial, and every step of chunk c + 1 queues behind chunk c's k_correct;
+//  * the fused kernel touches none of those follower-side buffers, and the table is read-only.
+// The join: ctx->stream waits for stream2's last step before anything else is queued on it (k_summary first), so whoever orders
+// work behind ctx->stream or waits for it sees a finished batch, as before.  Also after an error: what was forked is joined.
+#ifndef RC_PIPE_DEFAULT_CHUNKS
+#define RC_PIPE_DEFAULT_CHUNKS 0  // chunks of a batch of RC_PIPE_MIN_READS reads or more where RC_PIPELINE_CHUNKS says nothing (0: off;
+                                  // profiles/pipeline_chunks_ab.txt: no chunk count gained on any preset)
+#endif
+#ifndef RC_PIPE_MIN_READS
+#define RC_PIPE_MIN_READS (1u << 22)  // below this a batch's kernels are too short to pay C launches of the persistent kernels
+#endif
+#ifndef RC_PIPE_DEFAULT_GRID_DIV
+#define RC_PIPE_DEFAULT_GRID_DIV 1
+#endif
+static int rc_pipe_chunks(const rc_ctx *ctx, const rc_device_batch_args &a)
+{
+    if (ctx->env_pipe_chunks >= 0) return ctx->env_pipe_chunks;
+    return a.n >= RC_PIPE_MIN_READS ? RC_PIPE_DEFAULT_CHUNKS : 0;
+}
+
+static int rc_correct_pipelined(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbytes, int C, bool *ran)
+{
+    *ran = false;
+    uint32_t rpt = 0;
+    const uint32_t n_tiles = rc_fused_tiles(ctx, a, &rpt);
+    // (the lists need the classification; the traced and the instrumented k_correct are read back by the host step by step)
+    if (C < 2 || !n_tiles || !a.ret || ctx->trace_cap != 0 || ctx->env_no_classify || ctx->phase_prof) return RC_OK;
+    int rc;
+    ctx->work_stride = ((size_t)a.n + 63) & ~(size_t)63;
+    // follower-side buffers at their size for the whole batch, before the fork: a reallocation syncs ctx->stream alone
+    if ((rc = rc_dbuf_reserve(ctx, &ctx->worklist, ctx->work_stride * RC_WORK_CLASSES * 4 + 256))) return rc;
+    if ((rc = rc_dbuf_reserve(ctx, &ctx->tier_flag, (size_t)a.n + 256))) return rc;
+    auto tile_at = [&](int c) { return (uint32_t)((uint64_t)n_tiles * (uint32_t)c / (uint32_t)C); };
+    int c_first = -1, c_last = -1;  // (C > tiles: some chunks are empty; they launch nothing)
+    for (int c = 0; c < C; ++c)
+        if (tile_at(c + 1) > tile_at(c)) {
+            if (c_first < 0) c_first = c;
+            c_last = c;
+        }
+    ctx->thr_ready = true;  // (the fused kernel of a read's chunk has run before any follower kernel looks at the read)
+    bool forked = false;
+    auto chunks = [&]() -> int {
+        for (int c = c_first; c <= c_last; ++c) {
+            rc_chunk ch;
+            ch.st = ctx->stream2;
+            ch.tile_lo = tile_at(c);
+            ch.tile_hi = tile_at(c + 1);
+            if (ch.tile_hi == ch.tile_lo) continue;
+            ch.first = c == c_first;
+            ch.last = c == c_last;
+            ch.grid_div = ctx->env_pipe_grid_div > 0 ? ctx->env_pipe_grid_div : RC_PIPE_DEFAULT_GRID_DIV;
+            bool fused = false;
+            int e;
+            if ((e = rc_launch_probe_threshold_list(ctx, a, nbytes, &fused, &ch))) return e;
+            if (!fused || !ctx->cls_ready) {
+                rc_set_error(ctx, "correct: internal: the fused kernel refused a chunk of a batch it accepts");
+                return RC_ERR_STATE;
+            }
+            *ran = true;
+            const hipEvent_t ev = ctx->pipe_ev[ctx->pipe_ev_next++ % rc_ctx::RC_PIPE_EVENTS];
+            RC_CHECK_HIP(ctx, hipEventRecord(ev, ctx->stream));
+            RC_CHECK_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ev, 0));
+            forked = true;
+            bool single_ran = false;
+            if ((e = rc_launch_single(ctx, a, &single_ran, &ch))) return e;
+            if ((e = rc_launch_compact_range(ctx, ch.st, (const uint8_t *)ctx->cls.p, ch.lo, ch.hi, (uint32_t *)ctx->worklist.p, ctx->work_stride,
+                                             (uint32_t *)((char *)ctx->work.p + RC_WORK_NWORK_OFF))))
+                return e;
+            if ((e = rc_launch_correct(ctx, a, &ch))) return e;
+        }
+        return RC_OK;
+    };
+    rc = chunks();
+    if (forked) {
+        const hipError_t e1 = hipEventRecord(ctx->pipe_join, ctx->stream2);
+        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(ctx->stream, ctx->pipe_join, 0) : e1;
+        if (e2 != hipSuccess) {
+            (void)hipStreamSynchronize(ctx->stream2);  // (no join in stream order: the host waits instead)
+            if (!rc) {
+                rc_set_error(ctx, "correct: joining the follower stream failed: %s", hipGetErrorString(e2));
+                rc = RC_ERR_HIP;
+            }
+        }
+    }
+    return rc;
+}
+
 // the correction kernels over a batch rc_correct_check has accepted, ctx's device current (rc_correct_observed)
 // qual_split / qual_base2 (quality-bit mode only): arena bytes from qual_split on have their bits at
 // byte qual_base2 of d_qual -- the second arena of a paired host batch, whose bit array is separate
@@ -165,6 +268,17 @@ int rc_correct_device_impl(rc_ctx *ctx, const rc_device_batch *b, uint32_t qual_
     if (locality) {
         if ((rc = rc_launch_locality_order(ctx, a, (size_t)b->nbytes))) return rc;
         loc_order_valid = true;
+        // the chunked pipeline where it is switched on and the batch qualifies (RC_EXP_PROBE_ONLY builds: never)
+#ifndef RC_EXP_PROBE_ONLY
+        bool piped = false;
+        if ((rc = rc_correct_pipelined(ctx, a, (size_t)b->nbytes, rc_pipe_chunks(ctx, a), &piped))) return rc;
+        if (piped) {
+            if ((rc = rc_launch_summary(ctx, a.ret, a.n))) return rc;
+            ctx->routes_state = rc_ctx::RC_ROUTES_WHOLE;
+            ctx->routes_n = a.n;
+            return RC_OK;
+        }
+#endif
         // probe + threshold + classification in one kernel where the reads fit it
         if ((rc = rc_launch_probe_threshold_list(ctx, a, (size_t)b->nbytes, &fused))) return rc;
         if (!fused && (rc = rc_launch_probe_list(ctx, a, (size_t)b->nbytes, (int32_t *)ctx->counts.p))) return rc;

@@ -161,7 +161,7 @@ int rc_launch_kmer_info(rc_ctx *ctx, const rc_device_batch_args &a);
 template <int RC_FUSED_TILE, int WAVES, bool EXT, int EC = 8, int DEDUP = 0, bool QUAD = false, int NT = RC_PROBE_THREADS>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_probe_threshold_list(rc_kernel_args A, size_t nbytes, const uint32_t *__restrict__ list,
                                                                            uint32_t reads_per_block, int32_t *__restrict__ counts, uint32_t tiles_per_xcd,
-                                                                           const uint2 *__restrict__ span)
+                                                                           const uint2 *__restrict__ span, uint32_t tile0, uint32_t tile1)
 {
     constexpr int NS = DEDUP ? DEDUP : 1;
     __shared__ unsigned long long s_key[NS];
@@ -184,8 +184,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
     const uint8_t *seq = A.seq;
     // tiles_per_xcd != 0 (RC_FUSED_XCD=1): workgroup b runs on XCD b % 8, so tile (b % 8) * tiles_per_xcd + b / 8 hands each XCD's L2
     // one contiguous stretch of the locality list (neighbouring tiles share most of their k-mers)
-    const uint32_t tile = tiles_per_xcd ? (blockIdx.x & 7u) * tiles_per_xcd + (blockIdx.x >> 3) : blockIdx.x;
-    if ((uint64_t)tile * reads_per_block >= A.n) return;  // (uniform: the last XCD's stretch may be short)
+    // tile0 / tile1: the launch is for tiles [tile0, tile1) of the list -- the whole list, or a chunk of the chunked pipeline
+    // (rc_correct_device_impl), whose launches tile the list between them.  A.n stays the batch's: a mate is addressed through it.
+    const uint32_t tile = tile0 + (tiles_per_xcd ? (blockIdx.x & 7u) * tiles_per_xcd + (blockIdx.x >> 3) : blockIdx.x);
+    if (tile >= tile1 || (uint64_t)tile * reads_per_block >= A.n) return;  // (uniform: the last XCD's stretch may be short)
     const uint32_t i0 = tile * reads_per_block;
     const uint32_t nr = A.n - i0 < reads_per_block ? A.n - i0 : reads_per_block;
     for (int c = t; c < (RC_FUSED_TILE + 64) / 4; c += NT) s_raw[c] = 0;
@@ -584,7 +586,27 @@ int rc_launch_threshold(rc_ctx *ctx, const rc_device_batch_args &a, bool classif
 
 // K1 + K2 in one kernel over the locality list (ctx->loc_list); *done = false if the batch does not fit it
 // (a.max_len: the longest read of the tier the launch is for, at most 160 bases)
-int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbytes, bool *done)
+// reads per tile of the fused kernel: a read takes its bases, the NUL and up to 6 bytes of alignment; whole passes
+// of the 16-row threshold code (mates stay together); the small arena unless the large one holds twice the reads
+static uint32_t rc_fused_fit(int tile, int max_len)
+{
+    uint32_t r = (uint32_t)((tile - 8) / (max_len + 8));
+    if (r > RC_PLIST_MAX_READS) r = RC_PLIST_MAX_READS;
+    return r & ~15u;
+}
+
+uint32_t rc_fused_tiles(const rc_ctx *ctx, const rc_device_batch_args &a, uint32_t *reads_per_tile)
+{
+    const int ec = rc_short_ec(ctx, a.max_len, ctx->k);
+    *reads_per_tile = 0;
+    if (a.n == 0 || !ec || ctx->k < 4 || ctx->env_k2_wave_per_read || ctx->env_no_fuse) return 0;
+    uint32_t rpb = rc_fused_fit(2816, a.max_len) < 32 && rc_fused_fit(4096, a.max_len) >= 32 ? rc_fused_fit(4096, a.max_len) : rc_fused_fit(2816, a.max_len);
+    if (ctx->env_wave_tiles && ec == 8 && !ctx->ext) rpb = 4;  // (the wave-tile instance)
+    *reads_per_tile = rpb;
+    return rpb ? (a.n + rpb - 1) / rpb : 0;
+}
+
+int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbytes, bool *done, rc_chunk *ch)
 {
     *done = false;
     ctx->cls_ready = false;
@@ -605,19 +627,23 @@ int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, s
         A.runs = (uint2 *)ctx->runs.p;
         ctx->cand_ready = true;
     }
-    // reads per workgroup: a read takes its bases, the NUL and up to 6 bytes of alignment; whole passes
-    // of the 16-row threshold code (mates stay together); the small arena unless the large one holds
-    // twice the reads
-    auto fit = [&](int tile) {
-        uint32_t r = (uint32_t)((tile - 8) / (a.max_len + 8));
-        if (r > RC_PLIST_MAX_READS) r = RC_PLIST_MAX_READS;
-        return r & ~15u;
-    };
+    auto fit = [&](int tile) { return rc_fused_fit(tile, a.max_len); };  // reads per workgroup
     const bool large = fit(2816) < 32 && fit(4096) >= 32;
-    const uint32_t rpb = large ? fit(4096) : fit(2816);
+    const bool wave_tiles = ctx->env_wave_tiles && ec == 8 && !ctx->ext;
+    const uint32_t rpb = wave_tiles ? 4 : (large ? fit(4096) : fit(2816));
     if (rpb == 0) return RC_OK;  // (not reached: 16 reads of 160 bases fit)
-    rc_timer_begin(ctx);
-    const uint32_t n_tiles = (a.n + rpb - 1) / rpb;
+    // the tiles of this launch: all of them, or the chunk's (whose list positions the caller learns)
+    const uint32_t all_tiles = (a.n + rpb - 1) / rpb;
+    const uint32_t tile0 = ch ? ch->tile_lo : 0, tile1 = ch ? (ch->tile_hi < all_tiles ? ch->tile_hi : all_tiles) : all_tiles;
+    const uint32_t n_tiles = tile1 > tile0 ? tile1 - tile0 : 0;
+    if (ch) {
+        ch->lo = (uint64_t)tile0 * rpb < a.n ? tile0 * rpb : a.n;
+        ch->hi = (uint64_t)tile1 * rpb < a.n ? tile1 * rpb : a.n;
+    }
+    *done = true;
+    if (n_tiles == 0) return RC_OK;  // (an empty chunk)
+    const bool t_first = !ch || ch->first, t_last = !ch || ch->last;
+    rc_timer_begin_on(ctx, RC_T_PROBE, ctx->stream, t_first);
     const uint32_t txcd = ctx->env_fused_xcd ? (n_tiles + 7) / 8 : 0;
     const dim3 grid(txcd ? txcd * 8 : n_tiles), block(RC_PROBE_THREADS);
     const uint32_t *list = (const uint32_t *)ctx->loc_list.p;
@@ -632,31 +658,27 @@ int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, s
     //    tools/microbench_bucket.hip, but 57 more vector instructions per probe here: config 2 41.2 -> 47.0 ms, config 3 62.5 -> 77.4.
     const bool dedup = ctx->env_dedup > 0;
     const bool quad = ctx->env_quad > 0;
-    if (ctx->env_wave_tiles && ec == 8 && !ctx->ext) {  // dev: one wavefront, four reads, no inter-wave barrier (k <= 23-ish tables without extension bits)
-        const uint32_t rpw = 4;
-        const uint32_t nt = (a.n + rpw - 1) / rpw, tx = ctx->env_fused_xcd ? (nt + 7) / 8 : 0;
-        rc_timer_begin(ctx);
-        hipLaunchKernelGGL((k_probe_threshold_list<704, 6, false, 8, 0, false, 64>), dim3(tx ? tx * 8 : nt), dim3(64), 0, ctx->stream, A, nbytes,
-                           (const uint32_t *)ctx->loc_list.p, rpw, (int32_t *)ctx->counts.p, tx, (const uint2 *)ctx->loc_span.p);
-        rc_timer_end(ctx, RC_T_PROBE);
+    if (wave_tiles) {  // dev: one wavefront, four reads, no inter-wave barrier (k <= 23-ish tables without extension bits)
+        hipLaunchKernelGGL((k_probe_threshold_list<704, 6, false, 8, 0, false, 64>), grid, dim3(64), 0, ctx->stream, A, nbytes,
+                           (const uint32_t *)ctx->loc_list.p, rpb, (int32_t *)ctx->counts.p, txcd, (const uint2 *)ctx->loc_span.p, tile0, tile1);
+        rc_timer_end_on(ctx, RC_T_PROBE, ctx->stream, t_last);
         RC_CHECK_HIP(ctx, hipGetLastError());
-        *done = true;
         return RC_OK;
     }
 #define RC_FUSED_LAUNCH(TILE, WAVES, EXT, EC)                                                                                                        \
     do {                                                                                                                                             \
         if (dedup)                                                                                                                                   \
-            hipLaunchKernelGGL((k_probe_threshold_list<TILE, 5, EXT, EC, 1024>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p);         \
+            hipLaunchKernelGGL((k_probe_threshold_list<TILE, 5, EXT, EC, 1024>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p, tile0, tile1);         \
         else if (quad)                                                                                                                               \
-            hipLaunchKernelGGL((k_probe_threshold_list<TILE, WAVES, EXT, EC, 0, true>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p);  \
+            hipLaunchKernelGGL((k_probe_threshold_list<TILE, WAVES, EXT, EC, 0, true>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p, tile0, tile1);  \
         else                                                                                                                                         \
-            hipLaunchKernelGGL((k_probe_threshold_list<TILE, WAVES, EXT, EC, 0>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p);        \
+            hipLaunchKernelGGL((k_probe_threshold_list<TILE, WAVES, EXT, EC, 0>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p, tile0, tile1);        \
     } while (0)
     if (large) {  // (reads of up to 119 bases: at most 116 k-mers; 32 reads a tile: their k-mers would want a set of 2 048 slots -- not built)
         if (ctx->ext)
-            hipLaunchKernelGGL((k_probe_threshold_list<4096, 6, true, 8, 0>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p);
+            hipLaunchKernelGGL((k_probe_threshold_list<4096, 6, true, 8, 0>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p, tile0, tile1);
         else
-            hipLaunchKernelGGL((k_probe_threshold_list<4096, 6, false, 8, 0>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p);
+            hipLaunchKernelGGL((k_probe_threshold_list<4096, 6, false, 8, 0>), grid, block, 0, ctx->stream, A, nbytes, list, rpb, counts, txcd, (const uint2 *)ctx->loc_span.p, tile0, tile1);
     } else if (ec == 8) {
         if (ctx->ext)
             RC_FUSED_LAUNCH(2816, RC_FUSED_EXT_WAVES, true, 8);
@@ -674,9 +696,8 @@ int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, s
             RC_FUSED_LAUNCH(2816, RC_FUSED_SMALL_WAVES, false, 10);
     }
 #undef RC_FUSED_LAUNCH
-    rc_timer_end(ctx, RC_T_PROBE);
+    rc_timer_end_on(ctx, RC_T_PROBE, ctx->stream, t_last);
     RC_CHECK_HIP(ctx, hipGetLastError());
-    *done = true;
     return RC_OK;
 }
 
@@ -684,8 +705,9 @@ int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, s
 
 // K2s: finish the reads whose correction is one isolated substitution per untrusted stretch (rc_single.h); they leave
 // the work list before it is compacted.  Needs the classification (cls) and K1's counts of the listed reads.
-int rc_launch_single(rc_ctx *ctx, const rc_device_batch_args &a, bool *ran)
+int rc_launch_single(rc_ctx *ctx, const rc_device_batch_args &a, bool *ran, const rc_chunk *ch)
 {
+    const hipStream_t st = ch ? ch->st : ctx->stream;
     *ran = false;
     if (a.n == 0 || !ctx->cls_ready || !ctx->cand_ready || ctx->env_no_single) return RC_OK;
     const int ec = rc_short_ec(ctx, a.max_len, ctx->k);
@@ -698,34 +720,40 @@ int rc_launch_single(rc_ctx *ctx, const rc_device_batch_args &a, bool *ran)
     const size_t stride = ((size_t)a.n + 63) & ~(size_t)63;
     if ((rc = rc_dbuf_reserve(ctx, &ctx->single_list, stride * 3 * 4 + 256))) return rc;
     uint32_t *d_n = (uint32_t *)((char *)ctx->work.p + RC_WORK_NSINGLE_OFF);
-    RC_CHECK_HIP(ctx, hipMemsetAsync(d_n, 0, 16, ctx->stream));
-    if ((rc = rc_launch_compact_flag(ctx, (const uint8_t *)ctx->cand.p, a.n, (uint32_t *)ctx->single_list.p, stride, d_n))) return rc;
+    RC_CHECK_HIP(ctx, hipMemsetAsync(d_n, 0, 16, st));
+    if (ch)
+        rc = rc_launch_compact_flag_range(ctx, st, (const uint8_t *)ctx->cand.p, ch->lo, ch->hi, (uint32_t *)ctx->single_list.p, stride, d_n);
+    else
+        rc = rc_launch_compact_flag(ctx, (const uint8_t *)ctx->cand.p, a.n, (uint32_t *)ctx->single_list.p, stride, d_n);
+    if (rc) return rc;
     A.cls = (uint8_t *)ctx->cls.p;
     A.runs = (uint2 *)ctx->runs.p;
     A.worklist = (const uint32_t *)ctx->single_list.p;
     A.work_stride = stride;
     A.n_work = d_n;
-    rc_timer_begin(ctx);
+    rc_timer_begin_on(ctx, RC_T_SINGLE, st, !ch || ch->first);
     unsigned g = (unsigned)ctx->n_cu * (unsigned)RC_K2S_GRID;  // (a few workgroups per CU slot; they walk the list, whose length stays on the device)
-    if (g > (a.n + 15) / 16) g = (a.n + 15) / 16;
+    if (ch && ch->grid_div > 1) g = g / (unsigned)ch->grid_div ? g / (unsigned)ch->grid_div : 1u;
+    const uint32_t n_here = ch ? ch->hi - ch->lo : a.n;
+    if (g > (n_here + 15) / 16) g = (n_here + 15) / 16;
     const dim3 grid(g), block(256);
     if (ec == 8) {
         if (ctx->ext)
-            hipLaunchKernelGGL((k_single<true, 8>), grid, block, 0, ctx->stream, A);
+            hipLaunchKernelGGL((k_single<true, 8>), grid, block, 0, st, A);
         else
-            hipLaunchKernelGGL((k_single<false, 8>), grid, block, 0, ctx->stream, A);
+            hipLaunchKernelGGL((k_single<false, 8>), grid, block, 0, st, A);
     } else if (ec == 9) {
         if (ctx->ext)
-            hipLaunchKernelGGL((k_single<true, 9>), grid, block, 0, ctx->stream, A);
+            hipLaunchKernelGGL((k_single<true, 9>), grid, block, 0, st, A);
         else
-            hipLaunchKernelGGL((k_single<false, 9>), grid, block, 0, ctx->stream, A);
+            hipLaunchKernelGGL((k_single<false, 9>), grid, block, 0, st, A);
     } else {
         if (ctx->ext)
-            hipLaunchKernelGGL((k_single<true, 10>), grid, block, 0, ctx->stream, A);
+            hipLaunchKernelGGL((k_single<true, 10>), grid, block, 0, st, A);
         else
-            hipLaunchKernelGGL((k_single<false, 10>), grid, block, 0, ctx->stream, A);
+            hipLaunchKernelGGL((k_single<false, 10>), grid, block, 0, st, A);
     }
-    rc_timer_end(ctx, RC_T_SINGLE);
+    rc_timer_end_on(ctx, RC_T_SINGLE, st, !ch || ch->last);
     RC_CHECK_HIP(ctx, hipGetLastError());
     *ran = true;
     return RC_OK;
@@ -745,23 +773,28 @@ int rc_launch_kmer_info(rc_ctx *ctx, const rc_device_batch_args &a)
     return RC_OK;
 }
 
-int rc_launch_correct(rc_ctx *ctx, const rc_device_batch_args &a)
+int rc_launch_correct(rc_ctx *ctx, const rc_device_batch_args &a, const rc_chunk *ch)
 {
     if (a.n == 0) return RC_OK;
+    const hipStream_t st = ch ? ch->st : ctx->stream;
     rc_kernel_args A;
     int rc = fill_args(ctx, a, A);
     if (rc) return rc;
     unsigned grid = (unsigned)ctx->n_cu * 4u * (unsigned)rc_k3_waves(ctx->trace_cap > 0 ? 1024 : A.cap_class);
     if (ctx->env_k3_grid_waves > 0 && ctx->env_k3_grid_waves < RC_K3_WAVES) grid = (unsigned)ctx->n_cu * 4u * (unsigned)ctx->env_k3_grid_waves;
+    // (under the pipeline the stack is sized by the undivided grid, chunk after chunk the same: it is never reallocated between
+    // a call's fork and its join)
+    const unsigned grid_full = grid > a.n ? a.n : grid;
+    if (ch && ch->grid_div > 1) grid = grid / (unsigned)ch->grid_div ? grid / (unsigned)ch->grid_div : 1u;
     if (grid > a.n) grid = a.n;
     A.stack_frames = A.cap + 64;
-    rc = rc_dbuf_reserve(ctx, &ctx->stack, (size_t)grid * A.stack_frames * sizeof(rc_frame));
+    rc = rc_dbuf_reserve(ctx, &ctx->stack, (size_t)grid_full * A.stack_frames * sizeof(rc_frame));
     if (rc) return rc;
     A.stack = (rc_frame *)ctx->stack.p;
     // queue heads and phase counters to zero; the work-list length (written by the compaction) stays
-    RC_CHECK_HIP(ctx, hipMemsetAsync(ctx->work.p, 0, RC_WORK_NWORK_OFF, ctx->stream));
-    RC_CHECK_HIP(ctx, hipMemsetAsync((char *)ctx->work.p + RC_WORK_PHASE_OFF, 0, 34 * 8, ctx->stream));
-    RC_CHECK_HIP(ctx, hipMemsetAsync((char *)ctx->work.p + RC_WORK_PHASE_OFF + 64, 0xff, 16, ctx->stream));  // the two minima
+    RC_CHECK_HIP(ctx, hipMemsetAsync(ctx->work.p, 0, RC_WORK_NWORK_OFF, st));
+    RC_CHECK_HIP(ctx, hipMemsetAsync((char *)ctx->work.p + RC_WORK_PHASE_OFF, 0, 34 * 8, st));
+    RC_CHECK_HIP(ctx, hipMemsetAsync((char *)ctx->work.p + RC_WORK_PHASE_OFF + 64, 0xff, 16, st));  // the two minima
     A.phase_cycles = (unsigned long long *)((char *)ctx->work.p + RC_WORK_PHASE_OFF);
     if (ctx->cls_ready) {
         A.worklist = (const uint32_t *)ctx->worklist.p;
@@ -774,11 +807,11 @@ int rc_launch_correct(rc_ctx *ctx, const rc_device_batch_args &a)
         A.trace = (int32_t *)ctx->trace.p;
         A.trace_cap = ctx->trace_cap;
     }
-    rc_timer_begin(ctx);
+    rc_timer_begin_on(ctx, RC_T_CORRECT, st, !ch || ch->first);
     rc_k3_launcher special = nullptr;  // an instance compiled for this k and this table layout?
     if (ctx->trace_cap == 0 && !ctx->phase_prof && A.cap_class == 192 && !ctx->env_k3_generic) special = rc_k3_special(ctx->k, ctx->layout, ctx->ext);
     if (special)
-        special(dim3(grid), ctx->stream, A);
+        special(dim3(grid), st, A);
     else if (ctx->trace_cap > 0)
         hipLaunchKernelGGL((k_correct<1024, false, true>), dim3(grid), dim3(64), 0, ctx->stream, A);
     else if (ctx->phase_prof && A.cap_class == 192)
@@ -788,12 +821,12 @@ int rc_launch_correct(rc_ctx *ctx, const rc_device_batch_args &a)
     else if (ctx->phase_prof)
         hipLaunchKernelGGL((k_correct<1024, true, false>), dim3(grid), dim3(64), 0, ctx->stream, A);
     else if (A.cap_class == 192)
-        hipLaunchKernelGGL((k_correct<192, false, false>), dim3(grid), dim3(64), 0, ctx->stream, A);
+        hipLaunchKernelGGL((k_correct<192, false, false>), dim3(grid), dim3(64), 0, st, A);
     else if (A.cap_class == 320)
-        hipLaunchKernelGGL((k_correct<320, false, false>), dim3(grid), dim3(64), 0, ctx->stream, A);
+        hipLaunchKernelGGL((k_correct<320, false, false>), dim3(grid), dim3(64), 0, st, A);
     else
-        hipLaunchKernelGGL((k_correct<1024, false, false>), dim3(grid), dim3(64), 0, ctx->stream, A);
-    rc_timer_end(ctx, RC_T_CORRECT);
+        hipLaunchKernelGGL((k_correct<1024, false, false>), dim3(grid), dim3(64), 0, st, A);
+    rc_timer_end_on(ctx, RC_T_CORRECT, st, !ch || ch->last);
     if (ctx->phase_prof) {
         unsigned long long pc[34];
         uint32_t nwork = a.n, nsec[RC_WORK_CLASSES] = {0};

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rc_correct_core.h"
+#include "rc_timer_pool.h"
 
 #define RC_CHECK_HIP(ctx, expr)                                                                  \
     do {                                                                                         \
@@ -114,9 +115,15 @@ struct rc_batch_observed {
     void reset() { drop(RC_OBS_ALL, false); }
 };
 
-struct rc_kernel_timer {
-    double ms = 0;       // accumulated
-    uint64_t launches = 0;
+// the timer pool's back end (rc_timer_pool.h): HIP's events
+struct rc_hip_events {
+    typedef hipEvent_t event;
+    typedef hipStream_t stream;
+    bool create(event *e) { return hipEventCreate(e) == hipSuccess; }
+    void destroy(event e) { (void)hipEventDestroy(e); }
+    void record(event e, stream st) { (void)hipEventRecord(e, st); }
+    void wait(event e) { (void)hipEventSynchronize(e); }
+    bool elapsed(event a, event b, float *ms) { return hipEventElapsedTime(ms, a, b) == hipSuccess; }
 };
 
 enum { RC_T_PROBE = 0, RC_T_THRESH = 1, RC_T_CORRECT = 2, RC_T_SINGLE = 3, RC_T_WEAK = 4, RC_T_TRUST_PLANES = 5, RC_T_TRUST = 6, RC_T_DEPTH = 7, RC_T_SCREEN = 8, RC_T_NORM = 9, RC_T_COUNT };
@@ -143,13 +150,26 @@ struct rc_ctx : rc_table_desc {
     int k = 23;
     int n_cu = 256;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // Chunked pipeline (rc_correct_device_impl): the follower stream -- the compactions, k_single and k_correct of a chunk of the
+    // locality list run there while the fused probe + threshold kernel of the next chunks runs on `stream` -- a ring of events
+    // for the forks (chunk c's fused kernel is done) and the event of the join (`stream` waits for it before k_summary, so whoever
+    // orders work behind `stream`, or waits for it, has the follower's work too).  Created with the context.
+    hipStream_t stream2 = nullptr;
+    enum { RC_PIPE_EVENTS = 8 };
+    hipEvent_t pipe_ev[RC_PIPE_EVENTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, pipe_join = nullptr;
+    uint32_t pipe_ev_next = 0;
+    int env_pipe_chunks = -1;    // RC_PIPELINE_CHUNKS=<C>: 0 / 1 = off, C >= 2 = that many chunks at any batch size; -1: the default (RC_PIPE_*)
+    int env_pipe_grid_div = 0;   // RC_PIPELINE_GRID_DIV=<d> (dev / A-B): the follower kernels' grids divided by d under the pipeline; 0: the default
     bool profile = false;
     bool phase_prof = false;  // the instrumented build of k_correct runs (RC_PHASE_PROF=1 or rc_profile_enable(ctx, 2))
     bool phase_prof_print = false;  // ... and prints its per-phase cycle accounting (RC_PHASE_PROF=1, dev aid)
     uint64_t k3_listed = 0, k3_rounds = 0, k3_requests = 0;  // accumulated by the instrumented build
     int32_t *rounds_out = nullptr;  // rc_profile_read_rounds: where the instrumented build leaves every read's gather rounds
-    rc_kernel_timer timers[RC_T_COUNT];
+    // kernel timers: event pairs recorded now, waited for and added up later (rc_timer_resolve).  timer_open[kind] = the pair of
+    // that kind whose end is still to come (-1: none); timer_anon = rc_timer_begin's
+    rc_timer_pool<rc_hip_events, RC_T_COUNT> timers;
+    int timer_open[RC_T_COUNT];
+    int timer_anon = -1;
 
     rc_run_params P;
     bool params_set = false;
@@ -322,8 +342,15 @@ int rc_drain(rc_ctx *ctx);
 // page-locked host memory in 64 MB pieces, two in flight -- the bytes have then arrived on return, and a failure reads
 // "`what` failed: ..."
 int rc_copy_across(rc_ctx *ctx, void *dst, int dst_dev, const void *src, int src_dev, size_t n, hipStream_t st, const char *what);
+// Kernel timers (profiling on: rc_profile_enable).  Nothing here waits for the GPU: the pairs are resolved by rc_timer_resolve
+// -- rc_profile_get, rc_drain, a full pool.  rc_timer_begin / _end: one interval on ctx->stream.  rc_timer_begin_on / _end_on:
+// the interval of kind `which` on stream st, begun only if `first` and ended only if `last` -- the chunked pipeline launches a
+// kind's kernel once per chunk and times the span from its first launch to its last as ONE launch.
 void rc_timer_begin(rc_ctx *ctx);
 void rc_timer_end(rc_ctx *ctx, int which);
+void rc_timer_begin_on(rc_ctx *ctx, int which, hipStream_t st, bool first);
+void rc_timer_end_on(rc_ctx *ctx, int which, hipStream_t st, bool last);
+void rc_timer_resolve(rc_ctx *ctx);
 // f(std::bool_constant<ext>{}): the launch of a kernel that is compiled for tables with and without remainder-extension bits
 // (rc_device.h: EXT), written once -- rc_with_ext(ctx->ext, [&](auto ext) { ... k_probe<decltype(ext)::value> ... });
 template <class F>
@@ -363,6 +390,10 @@ int rc_launch_probe_tier(rc_ctx *ctx, const struct rc_device_batch_args &a, size
 int rc_launch_compact(rc_ctx *ctx, const uint8_t *d_cls, uint32_t n, uint32_t *d_list, size_t stride, uint32_t *d_count);
 int rc_launch_compact_local(rc_ctx *ctx, const uint8_t *d_cls, uint32_t n, uint32_t *d_list, size_t stride, uint32_t *d_count);
 int rc_launch_compact_flag(rc_ctx *ctx, const uint8_t *d_flag, uint32_t n, uint32_t *d_list, size_t stride, uint32_t *d_count);
+// the two compactions over positions [lo, hi) of the batch's locality order alone (ctx->loc_list), on stream st: the lists
+// receive the reads at those positions whose flag says so
+int rc_launch_compact_range(rc_ctx *ctx, hipStream_t st, const uint8_t *d_cls, uint32_t lo, uint32_t hi, uint32_t *d_list, size_t stride, uint32_t *d_count);
+int rc_launch_compact_flag_range(rc_ctx *ctx, hipStream_t st, const uint8_t *d_flag, uint32_t lo, uint32_t hi, uint32_t *d_list, size_t stride, uint32_t *d_count);
 
 // rc_count.hip
 int rc_count_begin(rc_ctx *ctx);
@@ -400,9 +431,22 @@ struct rc_device_batch_args {
     const uint32_t *tier_list = nullptr, *tier_n = nullptr;
 };
 int rc_launch_threshold(rc_ctx *ctx, const rc_device_batch_args &a, bool classify);
-int rc_launch_correct(rc_ctx *ctx, const rc_device_batch_args &a);
-int rc_launch_single(rc_ctx *ctx, const rc_device_batch_args &a, bool *ran);
-int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbytes, bool *done);
+// One chunk of the chunked pipeline, as the launchers see it.  The fused kernel takes tiles [tile_lo, tile_hi) of the locality
+// list and says which list positions [lo, hi) those are; k_single and k_correct run on stream st over lists made of those
+// positions.  first / last: the chunk is the call's first / last (timers, rc_timer_begin_on); grid_div: the persistent
+// kernels' grids divided by it.  nullptr everywhere: the whole batch on ctx->stream.
+struct rc_chunk {
+    hipStream_t st = nullptr;
+    uint32_t tile_lo = 0, tile_hi = 0;
+    uint32_t lo = 0, hi = 0;
+    bool first = true, last = true;
+    int grid_div = 1;
+};
+int rc_launch_correct(rc_ctx *ctx, const rc_device_batch_args &a, const rc_chunk *ch = nullptr);
+int rc_launch_single(rc_ctx *ctx, const rc_device_batch_args &a, bool *ran, const rc_chunk *ch = nullptr);
+int rc_launch_probe_threshold_list(rc_ctx *ctx, const rc_device_batch_args &a, size_t nbytes, bool *done, rc_chunk *ch = nullptr);
+// tiles of the fused kernel over a batch (0: the batch does not fit it) -- what the chunks are cut from
+uint32_t rc_fused_tiles(const rc_ctx *ctx, const rc_device_batch_args &a, uint32_t *reads_per_tile);
 int rc_launch_summary(rc_ctx *ctx, const int32_t *d_ret, uint32_t n);
 int rc_launch_kmer_info(rc_ctx *ctx, const rc_device_batch_args &a);
 

@@ -921,13 +921,14 @@ __global__ __launch_bounds__(256) void k_compact_sections(const uint8_t *__restr
 
 template <int NS>
 static int rc_compact_sections(rc_ctx *ctx, const uint8_t *d_flag, uint32_t n, int first, int step, uint32_t *d_list, size_t stride, uint32_t *d_count,
-                               const uint32_t *d_values = nullptr)
+                               const uint32_t *d_values = nullptr, hipStream_t st = nullptr)
 {
-    RC_CHECK_HIP(ctx, hipMemsetAsync(d_count, 0, NS * sizeof(uint32_t), ctx->stream));
+    if (!st) st = ctx->stream;
+    RC_CHECK_HIP(ctx, hipMemsetAsync(d_count, 0, NS * sizeof(uint32_t), st));
     if (n == 0) return RC_OK;
     unsigned grid = (n + 4095u) / 4096u;
     if (grid > (unsigned)ctx->n_cu * 32u) grid = (unsigned)ctx->n_cu * 32u;
-    hipLaunchKernelGGL(k_compact_sections<NS>, dim3(grid), dim3(256), 0, ctx->stream, d_flag, n, first, step, d_list, stride, d_count, d_values);
+    hipLaunchKernelGGL(k_compact_sections<NS>, dim3(grid), dim3(256), 0, st, d_flag, n, first, step, d_list, stride, d_count, d_values);
     RC_CHECK_HIP(ctx, hipGetLastError());
     return RC_OK;
 }
@@ -952,6 +953,29 @@ int rc_launch_compact_local(rc_ctx *ctx, const uint8_t *d_cls, uint32_t n, uint3
     if (rc) return rc;
     hipLaunchKernelGGL(k_gather_u8, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_cls, (const uint32_t *)ctx->loc_list.p, n, (uint8_t *)ctx->tier_flag.p);
     return rc_compact_sections<RC_WORK_CLASSES>(ctx, (const uint8_t *)ctx->tier_flag.p, n, RC_WORK_CLASSES, -1, d_list, stride, d_count, (const uint32_t *)ctx->loc_list.p);
+}
+
+// The chunked pipeline's compactions (rc_correct_device_impl): positions [lo, hi) of the locality order alone.  The flags of the
+// reads there are gathered through the order into ctx->tier_flag (free: no length tiers where the pipeline runs; at most one
+// compaction is in flight, the follower stream being serial) and compacted with the order's entries as values, as above.
+template <int NS>
+static int rc_compact_range(rc_ctx *ctx, hipStream_t st, const uint8_t *d_flag, uint32_t lo, uint32_t hi, int first, int step, uint32_t *d_list, size_t stride,
+                            uint32_t *d_count)
+{
+    const uint32_t m = hi > lo ? hi - lo : 0;
+    int rc = rc_dbuf_reserve(ctx, &ctx->tier_flag, (size_t)m + 256);
+    if (rc) return rc;
+    const uint32_t *order = (const uint32_t *)ctx->loc_list.p + lo;
+    if (m) hipLaunchKernelGGL(k_gather_u8, dim3((m + 255) / 256), dim3(256), 0, st, d_flag, order, m, (uint8_t *)ctx->tier_flag.p);
+    return rc_compact_sections<NS>(ctx, (const uint8_t *)ctx->tier_flag.p, m, first, step, d_list, stride, d_count, order, st);
+}
+int rc_launch_compact_range(rc_ctx *ctx, hipStream_t st, const uint8_t *d_cls, uint32_t lo, uint32_t hi, uint32_t *d_list, size_t stride, uint32_t *d_count)
+{
+    return rc_compact_range<RC_WORK_CLASSES>(ctx, st, d_cls, lo, hi, RC_WORK_CLASSES, -1, d_list, stride, d_count);
+}
+int rc_launch_compact_flag_range(rc_ctx *ctx, hipStream_t st, const uint8_t *d_flag, uint32_t lo, uint32_t hi, uint32_t *d_list, size_t stride, uint32_t *d_count)
+{
+    return rc_compact_range<3>(ctx, st, d_flag, lo, hi, 1, 1, d_list, stride, d_count);
 }
 
 // section v - 1 (v = 1 .. 3) of d_list = the reads with d_flag[i] == v (k_single's list: by number of untrusted stretches)
