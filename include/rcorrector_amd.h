@@ -994,6 +994,9 @@ int rc_selftest_get_bound(rc_ctx *ctx, const int32_t *c, size_t n, double error_
  * RC_ERR_STATE (the text says which) when the arrays do not describe the whole batch: none has run, it failed, it ran in length tiers (a
  * read of more than 160 bases), without classification or without candidates, or n is not its number of reads. */
 int rc_debug_routes(rc_ctx *ctx, uint8_t *cls_out, uint8_t *cand_out, uint64_t *runs_out, uint32_t n);
+/* test support: the batches this context and its slot lanes ran as a chunked pipeline (RC_PIPELINE_CHUNKS) and the non-empty
+ * chunks those launched, since the context was made; host counters, nothing is launched or waited for. */
+int rc_debug_pipeline(rc_ctx *ctx, uint64_t *batches, uint64_t *chunks);
 
 /* test support: the device side of the packed boundary alone (rc_submit_packed / rc_wait_packed without a correction), through
  * the launchers the transports use; needs no table and no run parameters.  All pointers are host memory.  Runs, on the context's

@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "rc_correct_batch", "rc_set_slot_lanes", "rc_runtime_prepare", "rc_submit", "rc_wait", "rc_host_alloc", "rc_host_free", "rc_host_register", "rc_host_unregister", "rc_correct_batch_traced", "rc_correct_device", "rc_strong_threshold_device", "rc_probe_device", "rc_sync",
     "rc_strong_threshold_read", "rc_correct_read", "rc_kmer_info_read",
     "rc_pack_bases", "rc_submit_packed", "rc_wait_packed", "rc_apply_fixes",
-    "rc_profile_enable", "rc_profile_get", "rc_profile_reset", "rc_profile_correct_counters", "rc_profile_read_rounds", "rc_selftest_get_bound", "rc_debug_routes", "rc_summary",
+    "rc_profile_enable", "rc_profile_get", "rc_profile_reset", "rc_profile_correct_counters", "rc_profile_read_rounds", "rc_selftest_get_bound", "rc_debug_routes", "rc_debug_pipeline", "rc_summary",
     "rc_selftest_transport_packed", "rc_selftest_transport_bytes",
 ]
 
@@ -394,6 +394,7 @@ def load_library():
     L.rc_profile_read_rounds.argtypes = [vp, vp]
     L.rc_selftest_get_bound.argtypes = [vp, vp, sz, C.c_double, vp, vp]
     L.rc_debug_routes.argtypes = [vp, vp, vp, vp, C.c_uint32]
+    L.rc_debug_pipeline.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.rc_selftest_transport_packed.argtypes = [vp, vp, sz, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp]
     L.rc_selftest_transport_bytes.argtypes = [vp, vp, sz, C.c_uint32, vp, sz, C.c_uint32, vp, vp, C.c_uint32, vp, vp]
     L.rc_summary.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -1150,6 +1151,13 @@ class Context:
         cls, cand, runs = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint64)
         self._ck(self._L.rc_debug_routes(self._h, cls.ctypes.data, cand.ctypes.data, runs.ctypes.data, n))
         return cls, cand, runs
+
+    def debug_pipeline(self):
+        """Test support (rc_debug_pipeline): (batches, chunks) -- the batches this context and its slot lanes ran as a chunked
+        pipeline (RC_PIPELINE_CHUNKS) and the non-empty chunks those launched, since the context was made."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._L.rc_debug_pipeline(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def selftest_transport_packed(self, packed, nbytes, off, exc_pos, exc_chr, after, cap):
         """Test support (rc_selftest_transport_packed): the packed boundary's kernels alone.  Returns (unpacked, n_fix, fix_pos,

@@ -638,6 +638,22 @@ int rc_debug_routes(rc_ctx *ctx, uint8_t *cls_out, uint8_t *cand_out, uint64_t *
     return RC_OK;
 }
 
+// test support: how many batches this context and its slot lanes ran as a chunked pipeline (rc_correct_pipelined with *ran = true)
+// and how many non-empty chunks those launched.  Host integers: no device memory is read, no stream is touched.
+int rc_debug_pipeline(rc_ctx *ctx, uint64_t *batches, uint64_t *chunks)
+{
+    if (!ctx) return RC_ERR_ARG;
+    uint64_t b = ctx->pipe_batches, c = ctx->pipe_chunks;
+    for (const rc_ctx *ln : ctx->lane) {  // (the batches its slot lanes ran, as rc_summary adds them)
+        if (!ln) continue;
+        b += ln->pipe_batches;
+        c += ln->pipe_chunks;
+    }
+    if (batches) *batches = b;
+    if (chunks) *chunks = c;
+    return RC_OK;
+}
+
 int rc_summary(const rc_ctx *c, uint64_t *total_reads, uint64_t *total_corrections)
 {
     if (!c) return RC_ERR_ARG;

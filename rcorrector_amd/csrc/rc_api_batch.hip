@@ -126,6 +126,8 @@ static int rc_correct_pipelined(rc_ctx *ctx, const rc_device_batch_args &a, size
                 rc_set_error(ctx, "correct: internal: the fused kernel refused a chunk of a batch it accepts");
                 return RC_ERR_STATE;
             }
+            if (!*ran) ++ctx->pipe_batches;  // (rc_debug_pipeline: host integers, nothing on the device knows of them)
+            ++ctx->pipe_chunks;
             *ran = true;
             const hipEvent_t ev = ctx->pipe_ev[ctx->pipe_ev_next++ % rc_ctx::RC_PIPE_EVENTS];
             RC_CHECK_HIP(ctx, hipEventRecord(ev, ctx->stream));

@@ -160,6 +160,7 @@ struct rc_ctx : rc_table_desc {
     uint32_t pipe_ev_next = 0;
     int env_pipe_chunks = -1;    // RC_PIPELINE_CHUNKS=<C>: 0 / 1 = off, C >= 2 = that many chunks at any batch size; -1: the default (RC_PIPE_*)
     int env_pipe_grid_div = 0;   // RC_PIPELINE_GRID_DIV=<d> (dev / A-B): the follower kernels' grids divided by d under the pipeline; 0: the default
+    uint64_t pipe_batches = 0, pipe_chunks = 0;  // rc_debug_pipeline (test support): batches this context ran as a pipeline, non-empty chunks it launched
     bool profile = false;
     bool phase_prof = false;  // the instrumented build of k_correct runs (RC_PHASE_PROF=1 or rc_profile_enable(ctx, 2))
     bool phase_prof_print = false;  // ... and prints its per-phase cycle accounting (RC_PHASE_PROF=1, dev aid)

@@ -11,7 +11,10 @@ with that context's: results and routing are functions of a read's unit alone, w
 locality list is the min-hash order, which no test controls; the cases that need an idle chunk get it by construction: a
 batch whose reads are error-free but for one pair, run with one tile per chunk, so that every chunk but one has empty
 k_single / k_correct lists -- the first and the last ones too unless that pair sorts there, and two batches with different
-pairs are run."""
+pairs are run.
+
+That the pipeline ran at all is asserted through rc_debug_pipeline (batches run as a pipeline, non-empty chunks launched): a
+comparison of "C chunks" with "no chunks" holds trivially where the batch did not qualify and ran whole."""
 import functools
 import os
 import subprocess
@@ -120,6 +123,25 @@ def _equal(want, got, label):
         assert len(bad) == 0, "%s: %s differs at %s: want %s got %s" % (label, what, bad[:5], w[bad[:5]], g[bad[:5]])
 
 
+def reads_per_tile(max_len, wave_tiles=False):
+    """rc_fused_tiles (rc_correct.hip) restated: a read takes its bases, the NUL and up to 6 bytes of alignment, max_len + 8 bytes
+    of a tile of 2 816 bytes (8 of them not the reads'), at most RC_PLIST_MAX_READS = 64 reads, in whole passes of 16 rows; the
+    4 096-byte tile where it holds 32 reads and the small one does not.  150 bases: 2808 // 158 = 17 -> 16 reads a tile; 100
+    bases: 2808 // 108 = 26 -> 16, but 4088 // 108 = 37 -> 32, so the 4 096-byte instance with 32.  wave_tiles: the instance of
+    RC_FUSED_WAVE_TILES=1 (4 reads), taken for reads of at most 128 k-mers over a table without extension bits -- the caller's to know."""
+    fit = lambda tile: min((tile - 8) // (max_len + 8), 64) & ~15
+    assert max_len <= 160, "the fused kernel holds reads of up to 160 bases"
+    if wave_tiles:
+        return 4
+    return fit(4096) if fit(2816) < 32 <= fit(4096) else fit(2816)
+
+
+def chunks_expected(n, rpt, chunks):
+    """the non-empty chunks of n reads in tiles of rpt, cut at tile_at(c) = n_tiles * c // chunks (rc_correct_pipelined): every
+    chunk where there are at least as many tiles, else one per tile"""
+    return min(chunks, (n + rpt - 1) // rpt)
+
+
 def _routes(ctx, n, tiered):
     if tiered:   # (rc_debug_routes describes whole batches only)
         return None
@@ -141,6 +163,9 @@ def _check(monkeypatch, name, chunks, env=None, profile=False, tiered=False):
         res, work = _launch(ctx, d, arrays)
         ctx.sync()
         out[c] = (_fetch(res, work), _routes(ctx, n, tiered), [ctx.profile_get(kd) for kd in range(4)] if profile else None)
+        # the pipeline ran for the chunked context and for no other: one batch, every non-empty chunk launched once
+        ran = (0, 0) if c == 0 or tiered else (1, chunks_expected(n, reads_per_tile(arrays[2]), c))
+        assert ctx.debug_pipeline() == ran, "%s, RC_PIPELINE_CHUNKS=%d: (batches, chunks) run as a pipeline are %r, expected %r" % (name, c, ctx.debug_pipeline(), ran)
         ctx.close()
     _equal(want, out[chunks][0], "%s, %d chunks, against the oracle" % (name, chunks))
     _equal(out[0][0], out[chunks][0], "%s, %d chunks, against no chunks" % (name, chunks))
@@ -206,6 +231,8 @@ def test_two_calls_back_to_back_without_a_sync(oracle, monkeypatch):
     r2 = _launch(ctx, d2, a2)
     r3 = _launch(ctx, d1, a1)
     ctx.sync()
+    batches, chunks = ctx.debug_pipeline()
+    assert batches == 3 and chunks == 9, "three batches of 188, 188 and 188 tiles in three chunks each: %r" % ((batches, chunks),)
     _equal(list(want1[:4]) + [np.concatenate(want1[4:])], _fetch(*r1), "first call")
     _equal(list(want2[:4]) + [np.concatenate(want2[4:])], _fetch(*r2), "second call")
     _equal(list(want1[:4]) + [np.concatenate(want1[4:])], _fetch(*r3), "third call")
